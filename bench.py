@@ -17,6 +17,11 @@ trials (strong scaling), rounds of 262144 trials per GPU, one counter all-reduce
 multi-process one (polar_amd/montecarlo.py, one rank per GPU, torch.distributed all-reduce) and the native one
 (polar_get_bler_quick_multi_ex from rank 0, one worker thread per GPU, ncclAllReduce) — with `counters_equal_single_gpu`:
 a 65536-trial prefix decoded on ONE GPU must give exactly the sharded counters (counter-based inputs).
+
+A plain run measures the headline alone: set-up, warm-up, the timed steps, the result line. Everything else — the
+Monte-Carlo leg, the CPU baseline, the other BASELINE configurations, the one-codeword-per-call, host-batch and
+probability-domain records — runs only with `--full`. `--dump-outputs DIR` writes what the last timed step computed
+as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -49,10 +54,16 @@ def main():
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--waves-per-cu", type=int, default=0)
     ap.add_argument("--lds-log", type=int, default=0)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="codewords for the CPU baseline (-1 = auto, 0 = skip)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short timings of BASELINE.json configs 1, 2, 3, 5")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: codewords for the CPU baseline (-1 = auto, 0 = skip)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short timings of BASELINE.json configs 1, 2, 3, 5 and the host-path records")
     ap.add_argument("--only-config", default="", help="run ONE of the other configurations (" + ", ".join(OTHER_CONFIGS) + ") and print its record: the command tools/profile_configs.sh profiles")
-    ap.add_argument("--mc-trials", type=int, default=16777216, help="total trials of the end-to-end get_bler_quick leg, strong scaling (0 = skip): 64 rounds of 262144 at one GPU, 8 full rounds per GPU at eight")
+    ap.add_argument("--mc-trials", type=int, default=16777216, help="with --full: total trials of the end-to-end get_bler_quick leg, strong scaling (0 = skip): 64 rounds of 262144 at one GPU, 8 full rounds per GPU at eight")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the records beside the headline: the end-to-end Monte-Carlo leg, the CPU baseline, the other "
+                         "configurations, one codeword per call, host batches, the probability-domain paths (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of the decoded bits: at most 48 MiB)")
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="launcher / rendezvous / counter all-reduce only, on CPU over gloo: no kernel runs, the line carries "
                          "\"dry_run\": true and no throughput (tests/test_bench_launcher.py)")
@@ -79,7 +90,9 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        # a child process, not an exec: this one may already have opened the GPU (device_count above)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -275,7 +288,10 @@ def main():
         "note": "SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x kernel cycles), committed profile (profiles/traffic.json)",
     }
 
-    if args.mc_trials > 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, sent, counters, args.seed)
+
+    if args.full and args.mc_trials > 0:
         del llr, sent
         if world == 1:        # (with peers a failure on one rank cannot be contained here: the others wait in a collective)
             try:
@@ -312,9 +328,9 @@ def main():
             res[name] = {"error": f"{type(ex).__name__}: {ex}"[:500], "traceback_tail": traceback.format_exc()[-800:]}
             torch.cuda.synchronize()
 
-    if rank == 0 and world == 1 and args.cpu_sample != 0 and not hung:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0 and not hung:
         guarded("cpu_baseline", lambda: cpu_baseline(args, code, llr, out))
-    if rank == 0 and world == 1 and not args.no_other_configs and not hung:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and not hung:
         guarded("other_configs", lambda: other_configs(args, dev))
         guarded("one_codeword_per_call", lambda: latency_record(args, code))
         guarded("host_batch", lambda: host_batch_record(args, dev))
@@ -352,6 +368,23 @@ def emit_last_line(line):
         pass
     print(line, flush=True)
     os.dup2(2, 1)
+
+
+def dump_outputs(d, out, sent, counters, seed):
+    """What the timed path handed back after its last step, for comparing two builds output for output (same arguments = same
+    inputs): the decoded information bits of a fixed, seeded sample of rows (at most 32 MiB as float32), the number of bits of
+    EVERY decoded codeword that differ from the sent ones (at most 4 Mi rows), and the counters [block errors, runs] as the
+    timed steps left them (summed over the steps)."""
+    os.makedirs(d, exist_ok=True)
+    B, K = out.shape
+    rows = min(B, max(1, (32 << 20) // (4 * K)))
+    idx = np.sort(np.random.default_rng(seed).choice(B, rows, replace=False))
+    bits = out[torch.from_numpy(idx).to(out.device)].cpu().numpy().astype(np.float32)
+    nb = min(B, 1 << 22)
+    bit_err = (out[:nb] != sent[:nb]).sum(dim=1, dtype=torch.int32).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(d, "decoded_bits_sample.npy"), bits)
+    np.save(os.path.join(d, "bit_errors_per_codeword.npy"), bit_err)
+    np.save(os.path.join(d, "block_error_counters.npy"), counters.cpu().numpy().astype(np.float64))
 
 
 MC_GRID = [1.0, 1.25, 1.5, 1.75, 2.0]        # BASELINE configuration 4: Eb/N0 1:0.25:2 dB, L = 32 + CRC16
@@ -509,7 +542,7 @@ def dry_run(args, world, rank):
     # the end-to-end Monte-Carlo leg with a stand-in engine (no kernel): trial t is a "block error" at point i when a hash
     # of (t, i) says so — the rounds, the per-round counter all-reduce, the strided shards and the prefix comparison are real
     mc = None
-    if args.mc_trials > 0:
+    if args.full and args.mc_trials > 0:
         def engine(seed, t0, T, stride, ebno, Ls, enabled, err, run):
             t = (np.arange(T, dtype=np.uint64) * np.uint64(stride) + np.uint64(t0))
             for li in range(len(Ls)):

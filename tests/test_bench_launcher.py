@@ -18,7 +18,7 @@ def _run(*a, env=None):
 
 
 def test_plain_launch_with_gpus_2_runs_two_ranks():
-    r = _run("--gpus", "2", "--steps", "2", "--dry-run-gloo")
+    r = _run("--gpus", "2", "--steps", "2", "--dry-run-gloo", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["dry_run"] is True

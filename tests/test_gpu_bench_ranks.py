@@ -23,7 +23,7 @@ def test_n_ranks_on_one_gpu_give_the_single_gpu_counters(built_lib, world):
         e.pop(k, None)
     total = 2 * 262144 * world
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--shared-gpu-gloo", "--steps", "1",
-                        "--warmup", "1", "--batch", "4096", "--mc-trials", str(total)],
+                        "--warmup", "1", "--batch", "4096", "--full", "--mc-trials", str(total)],
                        capture_output=True, text=True, timeout=900, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -66,7 +66,7 @@ def test_a_native_leg_that_does_not_return_cannot_take_the_result_line_with_it(b
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--shared-gpu-gloo", "--steps", "1",
-                        "--warmup", "1", "--batch", "4096", "--mc-trials", str(262144 * world)],
+                        "--warmup", "1", "--batch", "4096", "--full", "--mc-trials", str(262144 * world)],
                        capture_output=True, text=True, timeout=900, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -74,3 +74,32 @@ def test_a_native_leg_that_does_not_return_cannot_take_the_result_line_with_it(b
     assert line["n_gpus"] == world and line["value"] > 0
     assert "deadline" in mc["native_multi"]["error"] and mc["native_multi_hung"] is True
     assert mc["counters_equal_single_gpu_detail"]["multiprocess"] is True and mc["multiprocess"]["rounds"] == 1
+
+
+def test_a_plain_run_is_the_headline_alone_and_dumps_the_same_outputs_twice(built_lib, tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline record and nothing beside it, K timed steps, ms_per_step.
+    --dump-outputs writes the last step's results as float .npy files, and two runs with the same arguments write the same."""
+    import numpy as np
+    e = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_FORCE_DIST"):
+        e.pop(k, None)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--batch", "8192", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=e, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["bler"]["runs"] == 2 * 8192
+        for k in ("monte_carlo", "cpu_baseline", "other_configs", "one_codeword_per_call", "host_batch", "p1_paths"):
+            assert k not in line, k
+        got = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(got) == {"decoded_bits_sample.npy", "bit_errors_per_codeword.npy", "block_error_counters.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert got["bit_errors_per_codeword.npy"].shape == (8192,)
+        assert got["block_error_counters.npy"].tolist() == [line["bler"]["block_errors"], line["bler"]["runs"]]
+        assert (got["block_error_counters.npy"][0] == 2 * (got["bit_errors_per_codeword.npy"] > 0).sum())
+        dumps.append(got)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

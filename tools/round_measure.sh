@@ -5,7 +5,7 @@
 T=${1:-r06}; O=gpurun_out/$T; mkdir -p $O
 sha256sum polar_amd/libpolar_amd.so > $O/lib_sha256.txt
 (timeout 1800 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3) > $O/gpu_tests.txt
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python bench.py --batch 524288 --cpu-sample 0 --no-other-configs --mc-trials 0 > $O/bench_b524288.json 2>> $O/bench.err
 bash tools/profile.sh ${T} --steps 2 --warmup 1 --no-other-configs --mc-trials 0 > /dev/null 2>&1
 bash tools/profile_configs.sh config1 config2 config2_b262144 config3 config5 config3_b262144 config5_b262144 > $O/profile_configs.log 2>&1
