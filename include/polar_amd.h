@@ -176,7 +176,7 @@ int polar_get_bler_quick_multi(polar_code_t *h, const int *devices, int n_dev, c
                                double *bler_out, double *ber_out, int *used_rccl);
 
 /* General form of the sweep: `constellation` 0 / POLAR_CONST_BPSK = BPSK over AWGN with the Eb/N0 axis of
- * PolarCode.cpp:744-753 (what the three entry points above simulate); POLAR_CONST_ASK{4,8,16}_GRAY (include/polar_synth.h) =
+ * PolarCode.cpp:744-753 (what the three entry points above simulate); POLAR_CONST_ASK{4,8,16}_{GRAY,SP} (include/polar_synth.h) =
  * the ASK Gray + BICM front end of PolarM/Constellation.m with the SNR axis and fresh info bits every run
  * (PolarM/main_MC_CC_Comparison.m:44-119: BASELINE configuration 5, sharded over the GPUs of the node from one host
  * process). devices == NULL: 0..n_dev-1 (with n_dev == 1: the handle's own device). Optional outputs (may be NULL):
@@ -221,7 +221,7 @@ int polar_mc_batch_ber(polar_code_t *h, uint64_t seed, uint64_t t0, long T, long
 
 /* ---- ASK Gray + BICM front end (PolarM/Constellation.m:84-93, 123-144; sweep conventions of
  * PolarM/main_MC_CC_Comparison.m:88-96) for the 16-ASK configuration: `constellation` is
- * POLAR_CONST_ASK{4,8,16}_GRAY (include/polar_synth.h), the sweep axis is the SNR in dB
+ * POLAR_CONST_ASK{4,8,16}_{GRAY,SP} (include/polar_synth.h), the sweep axis is the SNR in dB
  * (Eb/N0 = snr_db + 10log10(N/K) - 10log10(n_bits), main_MC_CC_Comparison.m:121), info bits are
  * fresh every run. Same counters/semantics as polar_mc_batch. */
 int polar_synth_bicm_llr_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B,
@@ -233,7 +233,7 @@ int polar_mc_batch_bicm(polar_code_t *h, int constellation, uint64_t seed, uint6
 /* ---- Monte-Carlo code construction (PolarM/PolarCode.m:143-196 `monte_carlo`, receiver 'bicm',
  * with the genie-aided SC decoder `polar_decode_monte` :897-914). No handle: the result is what a
  * code is built FROM. For runs trial0 .. trial0+num_runs-1 (counter-based inputs, polar_synth.h):
- * N random message bits, polar transform, `constellation` (POLAR_CONST_BPSK or _ASK{4,8,16}_GRAY)
+ * N random message bits, polar transform, `constellation` (POLAR_CONST_BPSK or _ASK{4,8,16}_{GRAY,SP})
  * at the design SNR (sigma = sqrt(1/2) * 10^(-snr/20), n0 = sigma^2, :170), BICM p1, genie SC;
  * num_err[i] (host uint64 [2^n]) is INCREMENTED by the number of runs whose position i decided
  * wrongly — the table the reference writes to CodeConstructionData/MC_block_length_*.txt (:120-124)
@@ -242,6 +242,28 @@ int polar_mc_batch_bicm(polar_code_t *h, int constellation, uint64_t seed, uint6
  * summed across GPUs. */
 int polar_mc_construction(int n, int constellation, double design_snr_db, uint64_t seed, uint64_t trial0,
                           long num_runs, long batch, uint64_t *num_err);
+
+/* ---- multi-level coding (MLC) receiver (PolarM/main_MC_CC_Comparison.m:55-62, 98-110; PolarCode.m:155-161, 180-190) ----
+ * POLAR_RX_MLC OR-ed into the `constellation` argument of polar_get_bler_quick_multi_ex, polar_get_bler_quick_rank and
+ * polar_mc_construction selects the MLC receiver instead of BICM: nb = n_bits of the constellation component polar codes of
+ * length M = N / nb (message positions layer-major: component k owns positions k*M .. (k+1)*M - 1; the handle's frozen set
+ * is sliced the same way), component k carried by label bit k of the symbols, multistage SC decoding in the probability
+ * domain with each layer demapped conditioned on the re-encoded decisions of the layers below (Constellation.m:95-121).
+ * Construction: genie-aided per layer, counts layer-major. Sweep axis: SNR in dB, fresh info every run, list size 1 only.
+ * Workload definition: include/polar_synth.h. Refused with POLAR_E_ARG: a handle with crc_size > 0, a list size other than 1,
+ * an unknown constellation, N / nb not a power of two >= 2 (8-ASK at N = 1024).
+ * The entry points below take the constellation with or without the flag:
+ *   polar_encode_mlc      info [B][K] (host) -> coded [B][N] (host) in modulation order (symbol i, label bit k at i*nb + k);
+ *   polar_decode_mlc      received symbols y [B][M] (host), noise variance n0 -> decisions [B][K] as doubles (decode_sc_p1
+ *                         convention: 0.5 or NaN where a leaf is undecided), host pointers;
+ *   polar_decode_mlc_dev  the same on device pointers, stream-ordered on `stream`;
+ *   polar_synth_mlc_dev   the sweep's trials trial0 .. trial0+B-1 at `snr_db`: symbols [B][M] and sent info [B][K] (may be NULL). */
+#define POLAR_RX_MLC 0x100
+int polar_encode_mlc(polar_code_t *h, int constellation, const uint8_t *info, long B, uint8_t *coded);
+int polar_decode_mlc(polar_code_t *h, int constellation, const double *y, double n0, long B, double *out);
+int polar_decode_mlc_dev(polar_code_t *h, int constellation, const double *d_y, double n0, long B, double *d_out, void *stream);
+int polar_synth_mlc_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double snr_db,
+                        double *d_y, uint8_t *d_info, void *stream);
 
 /* tuning knobs (0 = default): waves resident per CU and LDS-resident layer exponent */
 int polar_set_tuning(polar_code_t *h, int waves_per_cu, int lds_log);

@@ -177,9 +177,20 @@ POLAR_SYNTH_FN double polar_synth_llr(double s, int coded_bit, double z) {
 #define POLAR_CONST_ASK16_GRAY 3
 #define POLAR_CONST_BPSK 4          /* Constellation.m:19 bpsk = [1 -1] (the default of the MC code construction) */
 #define POLAR_SYNTH_STREAM_MCINFO 3u
+/* set-partition labelling (Constellation.m:27,31-32): levels in ascending order, symbol index = level rank */
+#define POLAR_CONST_ASK4_SP 5
+#define POLAR_CONST_ASK8_SP 6
+#define POLAR_CONST_ASK16_SP 7
 
+/* bits per symbol; 0 for an id that is no constellation */
 POLAR_SYNTH_FN int polar_const_nbits(int id) {
-    return id == POLAR_CONST_BPSK ? 1 : (id == POLAR_CONST_ASK4_GRAY ? 2 : (id == POLAR_CONST_ASK8_GRAY ? 3 : 4));
+    switch (id) {
+        case POLAR_CONST_BPSK: return 1;
+        case POLAR_CONST_ASK4_GRAY: case POLAR_CONST_ASK4_SP: return 2;
+        case POLAR_CONST_ASK8_GRAY: case POLAR_CONST_ASK8_SP: return 3;
+        case POLAR_CONST_ASK16_GRAY: case POLAR_CONST_ASK16_SP: return 4;
+        default: return 0;
+    }
 }
 
 /* un-normalised integer levels (Constellation.m:21,25,29-30) and the sqrt() divisor */
@@ -193,9 +204,14 @@ POLAR_SYNTH_FN double polar_const_point(int id, int sym) {
     } else if (id == POLAR_CONST_ASK8_GRAY) {
         const int t[8] = {-7, -5, -1, -3, 7, 5, 1, 3};
         lvl = (double)t[sym & 7]; div = 21.0;
-    } else {
+    } else if (id == POLAR_CONST_ASK16_GRAY) {
         const int t[16] = {-15, -13, -9, -11, -1, -3, -7, -5, 15, 13, 9, 11, 1, 3, 7, 5};
         lvl = (double)t[sym & 15]; div = 85.0;
+    } else {
+        /* (-ns+1 : 2 : ns-1) / sqrt(div): ask4_sp, ask8_sp, ask16_sp */
+        const int ns = 1 << polar_const_nbits(id);
+        lvl = (double)(2 * (sym & (ns - 1)) - (ns - 1));
+        div = ns == 4 ? 5.0 : (ns == 8 ? 21.0 : 85.0);
     }
     return lvl / __builtin_sqrt(div);
 }
@@ -261,6 +277,45 @@ POLAR_SYNTH_FN void polar_synth_bicm_demap(int id, double norm, double y, double
 POLAR_SYNTH_FN void polar_synth_mc_info_word(uint64_t seed, uint64_t trial, uint32_t w, uint32_t out[4]) {
     polar_philox4x32(w, (uint32_t)trial, (uint32_t)(trial >> 32), POLAR_SYNTH_STREAM_MCINFO,
                      (uint32_t)seed, (uint32_t)(seed >> 32), out);
+}
+
+/* ===================== multi-level coding (MLC) receiver, set-partition ASK =====================
+ * Workload (PolarM/main_MC_CC_Comparison.m:55-62, 98-110; PolarCode.m:155-161, 180-190): nb = n_bits,
+ * M = N / nb. The N message positions are layer-major: component code k (0-based) owns positions
+ * k*M .. (k+1)*M-1 and its M coded bits are label bit k of the M symbols (symbol i carries bit k of
+ * component k's codeword at natural index i). Inputs of trial t:
+ *   sweep:         the K info bits are those of the BPSK/BICM sweep (polar_synth_info_word keyed by
+ *                  t / info_block_div), placed at the handle's info positions;
+ *   construction:  message bit j of the N is bit j of the polar_synth_mc_info_word stream of t,
+ *                  read layer-major (component k, position i = bit k*M + i);
+ *   symbol noise:  polar_synth_symbol_noise(seed, t, i), y_i = x_i + z_i * sigma.
+ *
+ * Conditioned demapper of layer k, Constellation.m:95-121: over the symbols in ascending index, those
+ * whose label bits 0..k-1 equal the decided coded bits u_lower[0..k-1] (doubles, compared as such)
+ * contribute exp(-|y-x|^2/2/n0) to p0 or p1 by label bit k; p1 = p1/(p0+p1), llr = log(p0/p1).
+ * The valid symbols are enumerated directly (s = t << k | low bits, t ascending): the same terms added in
+ * the same order as the reference's skip loop. A decided value other than exactly 0 or 1 (0.5 or NaN out
+ * of a leaf) matches no label: p0 = p1 = 0 and p1 = 0/0, as in the reference. Either output may be NULL. */
+POLAR_SYNTH_FN void polar_synth_mlc_demap(int id, double norm, double y, double n0, int k, const double *u_lower,
+                                          double *p1_out, double *llr_out) {
+    const int nb = polar_const_nbits(id);
+    double p0 = 0.0, p1 = 0.0;
+    int low = 0, any = 1;
+    for (int m = 0; m < k; ++m) {
+        if (u_lower[m] == 1.0) low |= 1 << m;
+        else if (!(u_lower[m] == 0.0)) any = 0;
+    }
+    if (any) {
+        for (int t = 0; t < (1 << (nb - k)); ++t) {
+            const int s = (t << k) | low;
+            double d = y - polar_const_point(id, s) / norm;
+            double ad = d < 0 ? -d : d;
+            double ps = polar_synth_exp_neg(-(ad * ad) / 2 / n0);
+            if ((t & 1) == 0) p0 = p0 + ps; else p1 = p1 + ps;
+        }
+    }
+    if (llr_out) *llr_out = polar_synth_log(p0 / p1);
+    if (p1_out) *p1_out = p1 / (p0 + p1);
 }
 
 /* N(0,1) variate for symbol `sym` of trial `trial` (one Box-Muller pair per two symbols) */

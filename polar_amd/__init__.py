@@ -26,7 +26,18 @@ _u64p = C.POINTER(C.c_uint64)
 
 
 ASK4_GRAY, ASK8_GRAY, ASK16_GRAY, BPSK = 1, 2, 3, 4   # include/polar_synth.h POLAR_CONST_*
-CONSTELLATION_NAMES = {"bpsk": BPSK, "ask4-gray": ASK4_GRAY, "ask8-gray": ASK8_GRAY, "ask16-gray": ASK16_GRAY}   # Constellation.m:41-59
+ASK4_SP, ASK8_SP, ASK16_SP = 5, 6, 7
+CONSTELLATION_NAMES = {"bpsk": BPSK, "ask4-gray": ASK4_GRAY, "ask8-gray": ASK8_GRAY, "ask16-gray": ASK16_GRAY,
+                       "ask4-sp": ASK4_SP, "ask8-sp": ASK8_SP, "ask16-sp": ASK16_SP}   # Constellation.m:41-66
+_NBITS = {BPSK: 1, ASK4_GRAY: 2, ASK4_SP: 2, ASK8_GRAY: 3, ASK8_SP: 3, ASK16_GRAY: 4, ASK16_SP: 4}   # polar_const_nbits
+RX_MLC = 0x100                 # include/polar_amd.h POLAR_RX_MLC
+RECEIVERS = ("bicm", "mlc")
+
+
+def _rx_flag(receiver):
+    if receiver not in RECEIVERS:
+        raise PolarError(f"unknown receiver {receiver!r} (supported: {RECEIVERS})")
+    return RX_MLC if receiver == "mlc" else 0
 
 
 def _constellation_id(c):
@@ -191,8 +202,7 @@ class PolarCode:
         meaning and defaults; the genie-aided SC runs on the GPU (mc_construction).
         With ``data_dir`` the table is read from / written to
         ``MC_block_length_<unique string>.txt`` exactly as the reference does (:111-124)."""
-        if receiver_algo != "bicm":
-            raise PolarError("only the 'bicm' receiver is built (SURVEY §2: the MLC demapper is out of scope)")
+        _rx_flag(receiver_algo)
         path = None
         if data_dir is not None:
             path = os.path.join(data_dir, "MC_block_length_" + construction_unique_string(
@@ -203,7 +213,7 @@ class PolarCode:
             n = int(round(np.log2(block_length)))
             if (1 << n) != block_length:
                 raise PolarError("block_length must be a power of two")
-            counts = mc_construction(n, design_snr_db, num_runs, constellation_name, seed=seed)
+            counts = mc_construction(n, design_snr_db, num_runs, constellation_name, seed=seed, receiver=receiver_algo)
             if path is not None:
                 write_construction_file(path, counts)
         if crc_size and crc_matrix is None:      # PolarCode.m:83: crc_matrix = floor(2*rand(crc_size, info_length))
@@ -347,6 +357,46 @@ class PolarCode:
         self._chk(self._L.polar_decode_sc_p1_batch(self._h, _p(a2, _dp), C.c_long(a2.shape[0]), _p(out, _dp)))
         return out[0] if single else out
 
+    # ---- multi-level coding receiver (PolarM/main_MC_CC_Comparison.m:55-62, 98-110) ---------
+    def encode_mlc(self, info, constellation):
+        """MLC encoder: info [B][K] (or [K]) -> coded bits [B][N] in modulation order (symbol i carries label bit k at
+        i*nb + k; component k = message positions k*M .. (k+1)*M - 1, M = N / nb)."""
+        a = np.ascontiguousarray(info, np.uint8)
+        single = a.ndim == 1
+        a2 = a.reshape(-1, self.K)
+        out = np.zeros((a2.shape[0], self.N), np.uint8)
+        self._chk(self._L.polar_encode_mlc(self._h, C.c_int(_constellation_id(constellation)), _p(a2, _u8p),
+                                           C.c_long(a2.shape[0]), _p(out, _u8p)))
+        return out[0] if single else out
+
+    def decode_mlc(self, y, n0, constellation):
+        """Multistage SC decoding of received symbols y [B][M] (or [M]) with noise variance n0 (= sigma^2): the K info
+        decisions as doubles, decode_sc_p1's convention (0.5 / NaN where a leaf is undecided)."""
+        cid = _constellation_id(constellation)
+        a = np.ascontiguousarray(y, np.float64)
+        single = a.ndim == 1
+        nb = _NBITS.get(cid, 0)
+        if nb and self.N % nb == 0:
+            # (the library copies B * M doubles from the caller's rows: a row of any other width is refused here; an unknown
+            # constellation or an N that nb does not divide is refused by the library before it reads anything)
+            M = self.N // nb
+            if a.ndim not in (1, 2) or a.shape[-1] != M:
+                raise PolarError(f"decode_mlc: y must be [B][{M}] or [{M}] (M = N / n_bits = {self.N} / {nb}), got shape {a.shape}")
+        a2 = a.reshape(1, -1) if single else a
+        out = np.zeros((a2.shape[0], self.K), np.float64)
+        self._chk(self._L.polar_decode_mlc(self._h, C.c_int(cid), _p(a2, _dp), C.c_double(n0), C.c_long(a2.shape[0]),
+                                           _p(out, _dp)))
+        return out[0] if single else out
+
+    def decode_mlc_dev(self, constellation, y_ptr, n0, B, out_ptr, stream=None):
+        self._chk(self._L.polar_decode_mlc_dev(self._h, C.c_int(_constellation_id(constellation)), C.c_void_p(y_ptr),
+                                               C.c_double(n0), C.c_long(B), C.c_void_p(out_ptr), _stream_ptr(stream)))
+
+    def synth_mlc_dev(self, constellation, seed, trial0, B, snr_db, y_ptr, info_ptr=0, stream=None):
+        self._chk(self._L.polar_synth_mlc_dev(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed),
+                                              C.c_uint64(trial0), C.c_long(B), C.c_double(snr_db), C.c_void_p(y_ptr),
+                                              C.c_void_p(info_ptr), _stream_ptr(stream)))
+
     # names used by BASELINE.json's north_star
     decode_SCL_LLR = decode_scl_llr
     decode_SCL_P1 = decode_scl_p1
@@ -406,14 +456,15 @@ class PolarCode:
                                         _p(enabled, _u8p), _p(err, _u64p), _p(bit_err, _u64p), _p(run, _u64p)))
 
     def get_bler_quick(self, ebno_vec, list_size_vec, max_runs=1000, max_err=100, seed=1, batch=None,
-                       return_ber=False, devices=None, constellation=None, return_counters=False):
+                       return_ber=False, devices=None, constellation=None, return_counters=False, receiver="bicm"):
         """PolarCode::get_bler_quick: returns bler[len(list_size_vec)][len(ebno_vec)] (PolarCode.cpp:658-785);
         with return_ber=True also PolarM's second output ber (PolarCode.m:781,848), same layout.
         batch=None: the library picks the rounds (see polar_amd.h). devices=[...]: shard the trials over these GPUs
         of the node from this one process (polar_get_bler_quick_multi_ex, RCCL all-reduce of the counters, one per round).
         constellation="ask16-gray" (...): the ASK Gray + BICM front end with `ebno_vec` read as the SNR axis in dB
-        (PolarM/main_MC_CC_Comparison.m:44-119). return_counters=True: additionally a dict with the raw counters
-        err / run (uint64, same layout) and the number of rounds."""
+        (PolarM/main_MC_CC_Comparison.m:44-119); receiver="mlc" with it: the multi-level coding receiver (list size 1).
+        return_counters=True: additionally a dict with the raw counters err / run (uint64, same layout) and the number of
+        rounds."""
         ebno = np.ascontiguousarray(ebno_vec, np.float64)
         Ls = np.ascontiguousarray(list_size_vec, np.uint8)
         shape = (len(Ls), len(ebno))
@@ -423,7 +474,7 @@ class PolarCode:
         run = np.zeros(shape, np.uint64)
         if batch is None:
             batch = 0
-        cid = 0 if constellation is None else _constellation_id(constellation)
+        cid = _sweep_id(constellation, receiver)
         if devices is not None:
             devs = np.ascontiguousarray(devices, np.int32)
             dptr, nd = devs.ctypes.data_as(C.POINTER(C.c_int)), len(devs)
@@ -442,7 +493,7 @@ class PolarCode:
         return res[0] if len(res) == 1 else res
 
     def get_bler_quick_rank(self, ebno_vec, list_size_vec, rank, world, reduce, max_runs=1000, max_err=100, seed=1, batch=None,
-                            constellation=None):
+                            constellation=None, receiver="bicm"):
         """polar_get_bler_quick_rank: this process is `rank` of `world` sharing the sweep; `reduce(a)` must SUM the uint64 numpy
         array `a` in place over the ranks (called collectively after every step). Returns (bler, ber, counters) like
         get_bler_quick(..., return_ber=True, return_counters=True)."""
@@ -463,7 +514,7 @@ class PolarCode:
             except Exception as ex:          # (no exception may cross the C frames)
                 failure.append(ex)
                 return 1
-        cid = 0 if constellation is None else _constellation_id(constellation)
+        cid = _sweep_id(constellation, receiver)
         rc = self._L.polar_get_bler_quick_rank(self._h, C.c_int(cid), C.c_int(rank), C.c_int(world), cb, None,
                                              _p(ebno, _dp), C.c_int(len(ebno)), _p(Ls, _u8p), C.c_int(len(Ls)),
                                              C.c_long(max_runs), C.c_long(max_err), C.c_uint64(seed), C.c_long(batch or 0),
@@ -472,6 +523,15 @@ class PolarCode:
             raise failure[0]
         _check(rc)
         return out, ber, {"err": err, "run": run, "rounds": int(rounds.value), "steps": self.debug_get("round_us_count")}
+
+
+def _sweep_id(constellation, receiver):
+    flag = _rx_flag(receiver)
+    if constellation is None:
+        if flag:
+            raise PolarError("the MLC receiver needs a constellation")
+        return 0
+    return _constellation_id(constellation) | flag
 
 
 # ---- Monte-Carlo code construction (PolarM/PolarCode.m:95-196) ---------------------------------
@@ -494,16 +554,18 @@ def write_construction_file(path, counts):
             f.write("%d \n" % int(c))
 
 
-def mc_construction(num_layers, design_snr_db, num_runs, constellation="bpsk", seed=1, trial0=0, batch=0, out=None):
+def mc_construction(num_layers, design_snr_db, num_runs, constellation="bpsk", seed=1, trial0=0, batch=0, out=None,
+                    receiver="bicm"):
     """Per-position error counts of the genie-aided SC decoder over ``num_runs`` Monte-Carlo runs
-    (PolarCode.m:143-196 `monte_carlo`, 'bicm' receiver), computed on the GPU. Returns uint64[N];
-    with ``out`` the counts are ADDED to it (shards of one trial range, see montecarlo.py)."""
+    (PolarCode.m:143-196 `monte_carlo`), computed on the GPU. Returns uint64[N];
+    with ``out`` the counts are ADDED to it (shards of one trial range, see montecarlo.py).
+    receiver="mlc": the genie-aided multistage decoder of the MLC receiver, counts layer-major (:155-161, 180-190)."""
     N = 1 << num_layers
     if out is None:
         out = np.zeros(N, np.uint64)
     if out.dtype != np.uint64 or out.shape != (N,) or not out.flags.c_contiguous:
         raise PolarError("out must be a contiguous uint64[N] array")
-    _check(lib().polar_mc_construction(C.c_int(num_layers), C.c_int(_constellation_id(constellation)),
+    _check(lib().polar_mc_construction(C.c_int(num_layers), C.c_int(_constellation_id(constellation) | _rx_flag(receiver)),
                                        C.c_double(design_snr_db), C.c_uint64(seed), C.c_uint64(trial0),
                                        C.c_long(num_runs), C.c_long(batch), _p(out, _u64p)))
     return out

@@ -342,6 +342,11 @@ int decode_impl(polar_code *h, const void *d_llr, int llr_f32, long B, const uns
                 double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase = 0, int *deferred = nullptr);
 bool use_sc_lat(const polar_code *h, long B);
 void fill_enc(const polar_code *h, PolarEncodeParams &p);
+// MLC receiver (polar_kernels_mlc.hip): *cid = the constellation without POLAR_RX_MLC, after the checks of include/polar_amd.h
+int mlc_check(const polar_code *h, int constellation, int *cid);
+void fill_mlc(const polar_code *h, int cid, double snr_db, PolarMlcParams &p);   // snr_db: sigma / n0 of the sweep's axis
+int mlc_decode_launch(polar_code *h, int cid, const double *d_y, double n0, long B, const unsigned int *n_dev, double *d_out,
+                      uint8_t *d_out_bytes, hipStream_t st);
 // polar_hostpipe.cpp
 void hostpipe_release(polar_code *h);
 // polar_multi.cpp

@@ -146,3 +146,36 @@ hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0,
 hipError_t polar_launch_mc_count_compact(const uint8_t *decoded, const uint8_t *sent, long B, int K,
                                          const uint64_t *alive_in, const unsigned *n_in, uint64_t *alive_out, unsigned *n_out,
                                          unsigned long long *ctr, hipStream_t st);
+
+// Multi-level coding receiver over set-partition (or Gray) ASK (polar_kernels_mlc.hip, include/polar_synth.h):
+// nb component codes of length M = N / nb = 2^m, component k = message positions k*M .. (k+1)*M - 1 (layer-major)
+struct PolarMlcParams {
+    int n, N, K, m, M, nb;
+    long B;
+    int constellation;           // POLAR_CONST_* (the receiver flag removed)
+    double sigma, n0, cnorm;
+    // front: trial of row b = sel[b] (alive lists) or trial0 + b*stride; info keyed by trial / info_block_div
+    uint64_t seed, trial0;
+    long stride, info_block_div;
+    const uint64_t *sel;
+    const unsigned int *n_dev;   // device: only the first min(B, *n_dev) rows exist, nullptr = B
+    const uint8_t *info;         // [B][K] device: given info bits (encode), nullptr = drawn from the sweep's info stream
+    uint8_t *info_out;           // [B][K] or nullptr
+    uint8_t *coded;              // [B][N] or nullptr: coded bits in modulation order (symbol i, label bit k at i*nb + k)
+    double *y;                   // [B][M] received symbols (front: written; decoders: read)
+    const uint8_t *frozen;       // [N]
+    const uint16_t *order;       // [N] (the first K entries are read)
+    double *out;                 // [B][K] doubles (decode_sc_p1 convention) or nullptr
+    uint8_t *out_bytes;          // [B][K] or nullptr: 0 / 1 for a decision of exactly 0.0 / 1.0, 2 otherwise
+    double *scr;                 // lane-per-codeword decoder: per-wave scratch [grid][polar_mlc_scr_doubles(N, nb) / 64][64]
+    // construction (genie): message bits packed [B][ceil(N/32)], per-position error counters [N] (layer-major)
+    uint32_t *minfo;
+    unsigned long long *num_err;
+    uint8_t *x_scr;              //   per-wave scratch [grid][2*M + (nb-1)*M][64] bytes
+};
+size_t polar_mlc_scr_doubles(int N, int nb);
+size_t polar_mlc_lat_lds_bytes(int N, int nb);
+hipError_t polar_launch_mlc_front(const PolarMlcParams &p, int mode, hipStream_t st);   // mode 0: sweep / encode, 1: construction
+hipError_t polar_launch_mlc_sc(const PolarMlcParams &p, int grid, hipStream_t st);
+hipError_t polar_launch_mlc_sc_lat(const PolarMlcParams &p, int grid, hipStream_t st);
+hipError_t polar_launch_mlc_genie(const PolarMlcParams &p, int grid, hipStream_t st);

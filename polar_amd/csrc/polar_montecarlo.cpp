@@ -90,6 +90,8 @@ struct McStage { int li, ie, slot; long T; uint64_t base; bool fresh; };
 static int mc_step_launch(polar_code_t *h, int constellation, uint64_t seed, const std::vector<McStage> &stages, int part, int parts,
                           const double *axis, int n_e, const uint8_t *Ls, int n_L, int n_slots, hipStream_t st) {
     const int N = h->N, K = h->K, P = n_e * n_L;
+    const bool mlc = (constellation & POLAR_RX_MLC) != 0;
+    const int cid = constellation & ~POLAR_RX_MLC;
     int rc;
     if ((rc = h->d_mc_ctr.ensure((size_t)2 * P))) return rc;
     HIP_TRY(hipMemsetAsync(h->d_mc_ctr.p, 0, (size_t)2 * P * sizeof(unsigned long long), st));
@@ -139,6 +141,19 @@ static int mc_step_launch(polar_code_t *h, int constellation, uint64_t seed, con
                 HIP_TRY(polar_launch_mc_init_alive(sl.list[0].p, h->d_slot_n.p + id, s.base + (uint64_t)part, parts, sl.cnt, st));
             }
             const bool reuse = s.fresh && off == 0 && shared && shared->ie == s.ie && shared->base == s.base && shared->T == s.T && shared_cnt == sl.cnt;
+            if (mlc) {
+                // MLC: the demapper is part of the decoder, so every stage decodes its own rows at its own SNR (symbols [cnt][M]
+                // at row `off`, decisions as bytes 0 / 1 / 2 for the counter below)
+                PolarMlcParams p;
+                fill_mlc(h, cid, axis[s.ie], p);
+                p.B = sl.cnt; p.seed = seed; p.sel = sl.list[sl.cur].p;
+                p.y = h->d_in.p + (size_t)off * N; p.info_out = h->d_bytes_a.p + (size_t)off * K;
+                if (!reuse) HIP_TRY(polar_launch_mlc_front(p, 0, st));
+                if (off == 0) { shared = s.fresh ? &s : nullptr; shared_cnt = sl.cnt; }
+                if ((rc = mlc_decode_launch(h, cid, p.y, p.n0, sl.cnt, nullptr, nullptr, h->d_out.p + (size_t)off * K, st))) return rc;
+                off += sl.cnt;
+                continue;
+            }
             if (!reuse) {
                 PolarEncodeParams p;
                 fill_enc(h, p);
@@ -150,7 +165,7 @@ static int mc_step_launch(polar_code_t *h, int constellation, uint64_t seed, con
             }
             off += sl.cnt;
         }
-        if ((rc = decode_impl(h, h->d_in.p, 0, rows, nullptr, Ls[li], h->d_out.p, nullptr, st, nullptr, nullptr))) return rc;
+        if (!mlc && (rc = decode_impl(h, h->d_in.p, 0, rows, nullptr, Ls[li], h->d_out.p, nullptr, st, nullptr, nullptr))) return rc;
         off = 0;
         for (const McStage *sp : ord) {
             const McStage &s = *sp;
@@ -205,14 +220,14 @@ int polar_mc_batch_ber(polar_code_t *h, uint64_t seed, uint64_t t0, long T, long
 int polar_mc_batch_bicm(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride,
                         const double *snr_db, int n_s, const uint8_t *Ls, int n_L,
                         const uint8_t *enabled, uint64_t *err, uint64_t *run) {
-    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_GRAY)
+    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_SP || constellation == POLAR_CONST_BPSK)
         return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
     return mc_batch_impl(h, constellation, seed, t0, T, stride, snr_db, n_s, Ls, n_L, enabled, err, nullptr, run);
 }
 int polar_synth_bicm_llr_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double snr_db,
                              double *d_llr, uint8_t *d_info, void *stream) {
     if (!h || !d_llr) return fail(POLAR_E_ARG, "NULL argument");
-    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_GRAY)
+    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_SP || constellation == POLAR_CONST_BPSK)
         return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
     if (B <= 0) return B == 0 ? POLAR_OK : fail(POLAR_E_ARG, "negative batch");
     DevGuard dg_;
@@ -226,11 +241,65 @@ int polar_synth_bicm_llr_dev(polar_code_t *h, int constellation, uint64_t seed, 
     return POLAR_OK;
 }
 
+// MLC construction (PolarCode.m:155-161, 180-190): per run nb x M random message bits, component encoding, genie-aided
+// multistage decoding; num_err layer-major
+static int mlc_construction(int n, int cid, double design_snr_db, uint64_t seed, uint64_t trial0, long num_runs, long batch,
+                            uint64_t *num_err) {
+    const int nb = (n >= 1 && n <= POLAR_MAX_N_LOG2 && !(cid & ~0xFF)) ? polar_const_nbits(cid) : 0;
+    if (nb == 0) return fail(POLAR_E_ARG, "unknown constellation %d", cid);
+    const int N = 1 << n, M = N / nb, words = (N + 31) / 32;
+    if (M * nb != N || M < 2 || (M & (M - 1)))
+        return fail(POLAR_E_ARG, "MLC: N = %d is not %d component codes of a power-of-two length >= 2", N, nb);
+    if (num_runs < 0 || batch < 0) return fail(POLAR_E_ARG, "negative run count");
+    if (num_runs == 0) return POLAR_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(POLAR_E_DEVICE, "no HIP device: the Monte-Carlo construction has no CPU path");
+    if (batch == 0) batch = std::max<long>(64, std::min<long>(32768, (256L << 20) / ((long)M * 8)));
+    batch = std::min(batch, num_runs);
+    const int grid = (int)std::min<long>((batch + 63) / 64, 8192);
+    DevBuf<double> d_y, d_scr;
+    DevBuf<uint32_t> d_info;
+    DevBuf<uint8_t> d_x;
+    DevBuf<unsigned long long> d_cnt;
+    int rc;
+    struct Guard {
+        DevBuf<double> &a, &b; DevBuf<uint32_t> &c; DevBuf<uint8_t> &d; DevBuf<unsigned long long> &e;
+        ~Guard() { a.release(); b.release(); c.release(); d.release(); e.release(); }
+    } guard{d_y, d_scr, d_info, d_x, d_cnt};
+    if ((rc = d_y.ensure((size_t)batch * M))) return rc;
+    if ((rc = d_info.ensure((size_t)batch * words))) return rc;
+    if ((rc = d_scr.ensure((size_t)grid * 2 * M * 64))) return rc;
+    if ((rc = d_x.ensure((size_t)grid * (2 * M + (nb - 1) * M) * 64))) return rc;
+    if ((rc = d_cnt.ensure((size_t)N))) return rc;
+    HIP_TRY(hipMemset(d_cnt.p, 0, (size_t)N * sizeof(unsigned long long)));
+    PolarMlcParams p;
+    memset(&p, 0, sizeof p);
+    p.n = n; p.N = N; p.nb = nb; p.M = M;
+    while ((1 << p.m) < M) ++p.m;
+    p.constellation = cid; p.seed = seed; p.stride = 1; p.info_block_div = 1;
+    p.sigma = std::sqrt(1.0 / 2) * std::pow(10.0, -design_snr_db / 20);          // PolarCode.m:170
+    p.n0 = p.sigma * p.sigma;
+    p.cnorm = polar_const_norm(cid);
+    p.y = d_y.p; p.minfo = d_info.p; p.scr = d_scr.p; p.x_scr = d_x.p; p.num_err = d_cnt.p;
+    for (long t = 0; t < num_runs; t += batch) {
+        p.B = std::min(batch, num_runs - t);
+        p.trial0 = trial0 + (uint64_t)t;
+        HIP_TRY(polar_launch_mlc_front(p, 1, nullptr));
+        HIP_TRY(polar_launch_mlc_genie(p, (int)std::min<long>((p.B + 63) / 64, grid), nullptr));
+    }
+    std::vector<unsigned long long> cnt(N);
+    HIP_TRY(hipMemcpy(cnt.data(), d_cnt.p, (size_t)N * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int i = 0; i < N; ++i) num_err[i] += (uint64_t)cnt[i];
+    return POLAR_OK;
+}
+
 int polar_mc_construction(int n, int constellation, double design_snr_db, uint64_t seed, uint64_t trial0,
                           long num_runs, long batch, uint64_t *num_err) {
     if (!num_err) return fail(POLAR_E_ARG, "NULL argument");
     if (n < 1 || n > POLAR_MAX_N_LOG2) return fail(POLAR_E_ARG, "n = %d out of range [1, %d]", n, POLAR_MAX_N_LOG2);
-    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_BPSK)
+    if (constellation & POLAR_RX_MLC) return mlc_construction(n, constellation & ~POLAR_RX_MLC, design_snr_db, seed, trial0, num_runs, batch, num_err);
+    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_SP)
         return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
     if (num_runs < 0 || batch < 0) return fail(POLAR_E_ARG, "negative run count");
     if (num_runs == 0) return POLAR_OK;
@@ -307,7 +376,12 @@ int bler_impl(polar_code_t *h, int constellation, const int *devices, int n_dev,
     if (n_e <= 0 || n_L <= 0 || max_runs <= 0 || batch < 0 || n_dev < 1) return fail(POLAR_E_ARG, "bad sizes");
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !reduce)) return fail(POLAR_E_ARG, "bad rank / world / reduce");
     if (constellation == POLAR_CONST_BPSK) constellation = 0;
-    if (constellation != 0 && (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_GRAY))
+    if (constellation & POLAR_RX_MLC) {
+        int cid, rc;
+        if ((rc = mlc_check(h, constellation, &cid))) return rc;
+        for (int i = 0; i < n_L; ++i)
+            if (Ls[i] != 1) return fail(POLAR_E_ARG, "the MLC receiver decodes with SC only (list size %d)", (int)Ls[i]);
+    } else if (constellation != 0 && (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_SP))
         return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
     for (int i = 0; i < n_L; ++i)
         if (Ls[i] < 1 || Ls[i] > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range", (int)Ls[i]);

@@ -81,7 +81,7 @@ def get_bler_quick_sharded(engine, ebno_vec, list_size_vec, max_runs=1000, max_e
 
 
 def get_bler_quick_ranks(code, ebno_vec, list_size_vec, max_runs=1000, max_err=100, seed=1, global_batch=None, device=None,
-                         stats=None, constellation=None):
+                         stats=None, constellation=None, receiver="bicm"):
     """The same sweep through the library's own driver (polar_get_bler_quick_rank): one process per GPU, this rank's device
     simulates the trials rank, rank + world, ... of every round, the rounds are PIPELINED on the device (a step decodes point 1
     of the newest round together with the later points of the rounds before it — polar_montecarlo.cpp mc_step_launch) and the
@@ -97,7 +97,7 @@ def get_bler_quick_ranks(code, ebno_vec, list_size_vec, max_runs=1000, max_err=1
             dist.all_reduce(t)
             a[:] = t.cpu().numpy().astype(np.uint64)
     bler, _, c = code.get_bler_quick_rank(ebno_vec, list_size_vec, rank, world, reduce, max_runs=max_runs, max_err=max_err, seed=seed,
-                                          batch=global_batch or 0, constellation=constellation)
+                                          batch=global_batch or 0, constellation=constellation, receiver=receiver)
     if stats is not None:
         stats["rounds"] = c["rounds"]
         stats["steps"] = c["steps"]
@@ -106,11 +106,12 @@ def get_bler_quick_ranks(code, ebno_vec, list_size_vec, max_runs=1000, max_err=1
     return bler, c["err"], c["run"]
 
 
-def mc_construction_sharded(counter, num_layers, design_snr_db, num_runs, constellation, seed=1, device=None):
+def mc_construction_sharded(counter, num_layers, design_snr_db, num_runs, constellation, seed=1, device=None, receiver="bicm"):
     """Monte-Carlo code construction (PolarCode.m:143-196) sharded over GPUs: runs 0..num_runs-1 are
     split into `world` contiguous ranges, rank r counts its range with
     counter(num_layers, design_snr_db, runs, constellation, seed=, trial0=) -> uint64[N]
-    (polar_amd.mc_construction on a GPU) and ONE all-reduce (sum, int64[N]) merges the tables.
+    (polar_amd.mc_construction on a GPU; receiver="mlc" is passed on as counter(..., receiver="mlc")) and ONE all-reduce
+    (sum, int64[N]) merges the tables.
     The runs are counter-based, so the table does not depend on the world size."""
     rank, world = _world()
     lo = (num_runs * rank) // world
@@ -118,7 +119,8 @@ def mc_construction_sharded(counter, num_layers, design_snr_db, num_runs, conste
     N = 1 << num_layers
     cnt = np.zeros(N, np.uint64)
     if hi > lo:
-        cnt = np.asarray(counter(num_layers, design_snr_db, hi - lo, constellation, seed=seed, trial0=lo), np.uint64)
+        kw = {"receiver": receiver} if receiver != "bicm" else {}
+        cnt = np.asarray(counter(num_layers, design_snr_db, hi - lo, constellation, seed=seed, trial0=lo, **kw), np.uint64)
     if world > 1:
         t = torch.from_numpy(cnt.astype(np.int64))
         if device is not None:
