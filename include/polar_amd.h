@@ -265,6 +265,44 @@ int polar_decode_mlc_dev(polar_code_t *h, int constellation, const double *d_y, 
 int polar_synth_mlc_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double snr_db,
                         double *d_y, uint8_t *d_info, void *stream);
 
+/* ---- Gaussian-approximation (GA) code construction (PolarM/PolarCode.m:198-255 `ga_code_construction`,
+ * GaussianApproximation/, CapacityHelper/, main_GA_CC_Comparison.m). No handle, like polar_mc_construction. fp64 on the
+ * device; grids and index rules in DESIGN.md §8b. Supported constellations: POLAR_CONST_BPSK, _ASK4_{GRAY,SP},
+ * _ASK16_{GRAY,SP}; 8-ASK (the reference splits N into thirds), N / n_bits below 2 and unknown ids give POLAR_E_ARG.
+ * sigma = sqrt(1/2) * 10^(-snr/20), n0 = sigma^2 (Constellation.m:251).
+ *   polar_bicm_capacity   get_bicm_capacity (Constellation.m:250-286): out[n][nb], integral over y_k = -ymax + k*dy,
+ *                         ymax = max(points) + 6 sigma + 1, dy = 0.1 sigma, P = floor(2 ymax / dy + 1e-9) + 1 points;
+ *   polar_mlc_capacity    get_mlc_capacity (:190-248): the same per layer, conditioned on the lower label bits, dy = 0.01 sigma;
+ *   polar_bpsk_capacity   get_bpsk_cap.m: out[n] (n0 = 10^(-snr/10) / 2, dy = 0.001 sqrt(n0), ymax = min(1e4, 4 + 3 sqrt(n0)));
+ *   polar_ga_phi_tables   initialize_phi.m at x step phi_dx: fwd[10002] (x = k * 0.01) and inv[100001] (largest x = k * phi_dx
+ *                         whose -log(phi) falls in bin ceil(-log(phi) / 1e-3), 0 where none does);
+ *   polar_polarized_counts  get_polarized_capacity (:288-370) for symbols trial0 .. trial0+num_sym-1 (the Monte-Carlo
+ *                         construction's runs at N = nb, include/polar_synth.h): u-LLR histograms counts[n][nb][801][2]
+ *                         (bin floor((clip(u, +-100) + 100) / 0.25), NaN -> bin 0; sent bit) are INCREMENTED, so disjoint
+ *                         seed or symbol ranges add up;
+ *   polar_polarized_capacity_from_counts  the entropy difference of those histograms, min(cap, 1) -> out[n][nb];
+ *   polar_polarized_capacity  both, for symbols 0 .. num_sym-1;
+ *   polar_ga_mean_llr     get_bpsk_llr_for_capacity.m: 4 * 10^(s_k / 10) for the first s_k = -20 + k * 0.01 whose BPSK capacity
+ *                         (polar_bpsk_capacity) reaches the value, s_4000 = 20 dB when none does;
+ *   polar_ga_construction the design points snr_db[n_points] of `constellation` (| POLAR_RX_MLC for the MLC receiver): the
+ *                         capacities (given in capacity[n_points][nb], or NULL: the integral for BPSK and MLC, the polarized
+ *                         capacity of 250 000 symbols of `seed` for multi-bit BICM), the mean LLRs, calculate_awgn_polarization
+ *                         per sub-block of N / nb with the phi tables of phi_dx, bit reversal -> channels[n_points][N]; the
+ *                         stable descending order of the channels -> order[n_points][N] (most reliable first); prefix sums
+ *                         of qfunc(sqrt(c) / sqrt(2)) along it -> bler_prefix[n_points][N] (entry K-1: the BLER estimate of
+ *                         K unfrozen positions). Any of the three outputs may be NULL. */
+int polar_bicm_capacity(int constellation, const double *snr_db, int n, double *out);
+int polar_mlc_capacity(int constellation, const double *snr_db, int n, double *out);
+int polar_bpsk_capacity(const double *snr_db, int n, double *out);
+int polar_ga_phi_tables(double phi_dx, double *fwd, double *inv);
+int polar_polarized_counts(int constellation, const double *snr_db, int n, long num_sym, uint64_t seed, uint64_t trial0,
+                           uint64_t *counts);
+int polar_polarized_capacity_from_counts(int constellation, int n, const uint64_t *counts, double *out);
+int polar_polarized_capacity(int constellation, const double *snr_db, int n, long num_sym, uint64_t seed, double *out);
+int polar_ga_mean_llr(const double *capacity, int n, double *mean_llr);
+int polar_ga_construction(int n, int constellation, const double *snr_db, int n_points, double phi_dx, uint64_t seed,
+                          const double *capacity, double *channels, uint16_t *order, double *bler_prefix);
+
 /* tuning knobs (0 = default): waves resident per CU and LDS-resident layer exponent */
 int polar_set_tuning(polar_code_t *h, int waves_per_cu, int lds_log);
 /* node arithmetic of decode_scl_llr: 0 = automatic (exp-domain kernel for list sizes >= 3, LLR-domain kernel

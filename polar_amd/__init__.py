@@ -237,6 +237,43 @@ class PolarCode:
         self.construction_counts, self.bler_estimate = new.construction_counts, new.bler_estimate
         return self.bler_estimate
 
+    @classmethod
+    def from_gauss_approx(cls, block_length, info_length, design_snr_db, constellation_name="bpsk", receiver_algo="bicm",
+                          crc_size=0, crc_matrix=None, phi_dx=1e-5, seed=1, capacity=None):
+        """Code designed by PolarM's `ga_code_construction` (PolarCode.m:198-255) on the GPU (ga_construction): capacities,
+        mean LLRs, Gaussian-approximation polarization per sub-block, stable descending sort; the first K+crc positions
+        are unfrozen and the order (most reliable first) is the handle's info-bit order, as from_counts passes it. Sets
+        ``bler_estimate`` (sum of qfunc(sqrt(c)/sqrt(2)) over the unfrozen channels) and ``channels``. ``capacity`` (one
+        value per label bit) replaces the computed capacities, e.g. by the reference's cached ones."""
+        n = int(round(np.log2(block_length)))
+        if (1 << n) != block_length:
+            raise PolarError("block_length must be a power of two")
+        cap = None if capacity is None else np.asarray(capacity, np.float64).reshape(1, -1)
+        ch, order, pre = ga_construction(n, [design_snr_db], constellation_name, receiver_algo, phi_dx, seed, cap)
+        k = info_length + crc_size
+        if not 0 < k <= block_length:
+            raise PolarError("info_length + crc_size must lie in [1, block_length]")
+        frozen = np.ones(block_length, np.uint8)
+        frozen[order[0, :k]] = 0
+        if crc_size and crc_matrix is None:      # PolarCode.m:83: crc_matrix = floor(2*rand(crc_size, info_length))
+            crc_matrix = np.random.default_rng(seed).integers(0, 2, (crc_size, info_length)).astype(np.uint8)
+        code = cls.from_tables(n, info_length, crc_size, frozen, order[0], crc_matrix)
+        code.channels = ch[0]
+        code.bler_estimate = float(pre[0, k - 1])
+        return code
+
+    def ga_code_construction(self, design_snr_db, constellation_name="bpsk", receiver_algo="bicm", phi_dx=1e-5, seed=1,
+                             capacity=None):
+        """In-place redesign of this code by the Gaussian approximation, as the reference method of the same name
+        (PolarCode.m:198-255): block length, K, crc size and the crc matrix are kept. Returns the BLER estimate."""
+        cm = self.crc_matrix if self.crc_size else None
+        new = PolarCode.from_gauss_approx(self.block_length, self.info_length, design_snr_db, constellation_name,
+                                          receiver_algo, self.crc_size, cm, phi_dx, seed, capacity)
+        self.close()
+        self._h, new._h = new._h, None
+        self.channels, self.bler_estimate = new.channels, new.bler_estimate
+        return self.bler_estimate
+
     def _chk(self, rc):
         if rc < 0:
             raise PolarError(f"polar_amd error {rc}: {self._L.polar_last_error().decode()}")
@@ -569,3 +606,188 @@ def mc_construction(num_layers, design_snr_db, num_runs, constellation="bpsk", s
                                        C.c_double(design_snr_db), C.c_uint64(seed), C.c_uint64(trial0),
                                        C.c_long(num_runs), C.c_long(batch), _p(out, _u64p)))
     return out
+
+
+# ---- Gaussian-approximation code construction (PolarM/PolarCode.m:198-255, main_GA_CC_Comparison.m) ---------------------
+GA_CONSTELLATIONS = ("bpsk", "ask4-gray", "ask4-sp", "ask16-gray", "ask16-sp")   # 8-ASK: refused (include/polar_amd.h)
+GA_BINS = 801                  # polarized capacity: u-LLR bins of width 0.25 over [-100, 100]
+
+
+def _ga_id(constellation):
+    cid = _constellation_id(constellation)
+    if cid not in (BPSK, ASK4_GRAY, ASK4_SP, ASK16_GRAY, ASK16_SP):
+        raise PolarError(f"constellation {constellation!r} is not supported by the GA construction (supported: {GA_CONSTELLATIONS})")
+    return cid
+
+
+def _snr_array(snr_db):
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(snr_db, np.float64)).reshape(-1))
+
+
+def _capacity(fn, constellation, snr_db):
+    cid = _ga_id(constellation)
+    snr = _snr_array(snr_db)
+    out = np.zeros((snr.size, _NBITS[cid]))
+    _check(getattr(lib(), fn)(C.c_int(cid), _p(snr, _dp), C.c_int(snr.size), _p(out, _dp)))
+    return out
+
+
+def bicm_capacity(constellation, snr_db):
+    """Constellation.get_bicm_capacity (Constellation.m:250-286) on the GPU: [len(snr_db)][n_bits]."""
+    return _capacity("polar_bicm_capacity", constellation, snr_db)
+
+
+def mlc_capacity(constellation, snr_db):
+    """Constellation.get_mlc_capacity (Constellation.m:190-248) on the GPU: [len(snr_db)][n_bits], layer by layer."""
+    return _capacity("polar_mlc_capacity", constellation, snr_db)
+
+
+def bpsk_capacity(snr_db=None):
+    """CapacityHelper/get_bpsk_cap.m on the GPU: [len(snr_db)]; None = the table of get_bpsk_llr_for_capacity.m
+    (-20 : 0.01 : 20 dB as -20 + k * 0.01, 4001 points)."""
+    snr = _snr_array(-20.0 + np.arange(4001) * 0.01 if snr_db is None else snr_db)
+    out = np.zeros(snr.size)
+    _check(lib().polar_bpsk_capacity(_p(snr, _dp), C.c_int(snr.size), _p(out, _dp)))
+    return out
+
+
+def ga_phi_tables(phi_dx=1e-5):
+    """initialize_phi.m on the GPU: (forward table [10002], inverse table [100001])."""
+    fwd, inv = np.zeros(10002), np.zeros(100001)
+    _check(lib().polar_ga_phi_tables(C.c_double(phi_dx), _p(fwd, _dp), _p(inv, _dp)))
+    return fwd, inv
+
+
+def polarized_counts(constellation, snr_db, num_sym, seed=1, trial0=0, out=None):
+    """u-LLR histograms of Constellation.get_polarized_capacity (Constellation.m:288-370) for symbols trial0 ..
+    trial0+num_sym-1: uint64 [len(snr_db)][n_bits][801][2] (bin, sent bit). With ``out`` they are ADDED to it, so disjoint
+    seeds or symbol ranges combine."""
+    cid = _ga_id(constellation)
+    snr = _snr_array(snr_db)
+    shape = (snr.size, _NBITS[cid], GA_BINS, 2)
+    if out is None:
+        out = np.zeros(shape, np.uint64)
+    if out.dtype != np.uint64 or out.shape != shape or not out.flags.c_contiguous:
+        raise PolarError(f"out must be a contiguous uint64{list(shape)} array")
+    _check(lib().polar_polarized_counts(C.c_int(cid), _p(snr, _dp), C.c_int(snr.size), C.c_long(num_sym), C.c_uint64(seed),
+                                        C.c_uint64(trial0), _p(out, _u64p)))
+    return out
+
+
+def polarized_capacity_from_counts(constellation, counts):
+    cid = _ga_id(constellation)
+    counts = np.ascontiguousarray(counts, np.uint64)
+    n = counts.shape[0]
+    if counts.shape != (n, _NBITS[cid], GA_BINS, 2):
+        raise PolarError("counts must be [n][n_bits][801][2]")
+    out = np.zeros((n, _NBITS[cid]))
+    _check(lib().polar_polarized_capacity_from_counts(C.c_int(cid), C.c_int(n), _p(counts, _u64p), _p(out, _dp)))
+    return out
+
+
+def polarized_capacity(constellation, snr_db, num_sym=250000, seed=1, data_dir=None):
+    """Constellation.get_polarized_capacity on the GPU: [len(snr_db)][n_bits]. With ``data_dir`` each SNR is read from /
+    written to ``<constellation>_snr_<num2str(snr)>.mat`` (variable cap_vec) as the reference does (:290-296, 367), which
+    needs scipy; without scipy data_dir is refused."""
+    snr = _snr_array(snr_db)
+    name = constellation if isinstance(constellation, str) else \
+        {v: k for k, v in CONSTELLATION_NAMES.items()}[_constellation_id(constellation)]
+    if data_dir is None:
+        return polarized_capacity_from_counts(constellation, polarized_counts(constellation, snr, num_sym, seed))
+    try:
+        import scipy.io
+    except ImportError as e:
+        raise PolarError("polarized_capacity(data_dir=...) reads and writes .mat files and needs scipy") from e
+    out = np.zeros((snr.size, _NBITS[_ga_id(constellation)]))
+    todo = []
+    for i, s in enumerate(snr):
+        path = os.path.join(data_dir, f"{name}_snr_{_num2str(s)}.mat")
+        if os.path.exists(path):
+            out[i] = scipy.io.loadmat(path)["cap_vec"].reshape(-1)[: out.shape[1]]
+        else:
+            todo.append(i)
+    if todo:
+        cap = polarized_capacity_from_counts(constellation, polarized_counts(constellation, snr[todo], num_sym, seed))
+        for j, i in enumerate(todo):
+            out[i] = cap[j]
+            scipy.io.savemat(os.path.join(data_dir, f"{name}_snr_{_num2str(snr[i])}.mat"), {"cap_vec": cap[j].reshape(-1, 1)})
+    return out
+
+
+def ga_mean_llr(capacity):
+    """get_bpsk_llr_for_capacity.m against the device's BPSK capacity table."""
+    cap = np.ascontiguousarray(capacity, np.float64)
+    out = np.zeros(cap.shape)
+    _check(lib().polar_ga_mean_llr(_p(cap, _dp), C.c_int(cap.size), _p(out, _dp)))
+    return out
+
+
+def ga_construction(num_layers, snr_db, constellation="bpsk", receiver="bicm", phi_dx=1e-5, seed=1, capacity=None):
+    """Gaussian-approximation construction of every design SNR in one launch (PolarCode.m:198-255): returns
+    (channels [P][N], order [P][N] stable descending = most reliable first, bler_prefix [P][N]); bler_prefix[p][K-1] is the
+    BLER estimate of the code with K unfrozen positions. ``capacity`` [P][n_bits] replaces the computed capacities."""
+    cid = _ga_id(constellation)
+    flag = _rx_flag(receiver)
+    snr = _snr_array(snr_db)
+    P, N = snr.size, 1 << num_layers
+    cap = None
+    if capacity is not None:
+        cap = np.ascontiguousarray(capacity, np.float64)
+        if cap.shape != (P, _NBITS[cid]):
+            raise PolarError(f"capacity must be [{P}][{_NBITS[cid]}]")
+    ch, order, pre = np.zeros((P, N)), np.zeros((P, N), np.uint16), np.zeros((P, N))
+    _check(lib().polar_ga_construction(C.c_int(num_layers), C.c_int(cid | flag), _p(snr, _dp), C.c_int(P),
+                                       C.c_double(phi_dx), C.c_uint64(seed), _p(cap, _dp) if cap is not None else None,
+                                       _p(ch, _dp), _p(order, _u16p), _p(pre, _dp)))
+    return ch, order, pre
+
+
+def ga_rate_table(rates=(1 / 32, 1 / 16, 1 / 8, 1 / 4, 2 / 4, 3 / 4, 7 / 8),
+                  constellations=("ask4-gray", "ask4-sp", "ask16-gray", "ask16-sp"), receivers=("bicm", "mlc", "bicm", "mlc"),
+                  snr_db_vec=None, target_bler=1e-5, block_length=1024, phi_dx=1e-5, seed=1, capacities=None):
+    """PolarM's main_GA_CC_Comparison.m on the GPU: one GA construction per (constellation, SNR), then per rate the
+    reference's walk over the SNR grid (from the previous rate's stopping index minus one, until the estimate of
+    K = ceil(rate * N) falls below the target) and its log interpolation. Returns a dict with ``snr_needed`` and
+    ``ebno_needed`` [rate][constellation] and ``flags``. Deviation: where the reference waits for a key press ('Possibly
+    too high starting SNR', flag 1, then interpolating with a stale estimate) or runs off the grid (flag 2), the entry is
+    NaN. ``capacities`` (a list of [len(snr_db_vec)][n_bits] arrays or None per constellation) replaces computed ones."""
+    if snr_db_vec is None:
+        snr_db_vec = -10.0 + np.arange(161) * 0.25
+    snr = _snr_array(snr_db_vec)
+    n = int(round(np.log2(block_length)))
+    Ks = [int(np.ceil(r * block_length)) for r in rates]
+    shape = (len(rates), len(constellations))
+    snr_needed, ebno, flags = np.full(shape, np.nan), np.full(shape, np.nan), np.zeros(shape, np.int64)
+    for ci, (c, rx) in enumerate(zip(constellations, receivers)):
+        cap = None if capacities is None else capacities[ci]
+        _, _, pre = ga_construction(n, snr, c, rx, phi_dx, seed, cap)
+        bler = pre[:, [k - 1 for k in Ks]]
+        snr_needed[:, ci], ebno[:, ci], flags[:, ci] = _rate_walk(bler, rates, snr, target_bler, _NBITS[_ga_id(c)])
+    return {"snr_needed": snr_needed, "ebno_needed": ebno, "flags": flags, "snr_db_vec": snr, "rates": np.asarray(rates)}
+
+
+def _rate_walk(bler, rates, snr_vec, target, nbits):
+    """main_GA_CC_Comparison.m:34-66 over bler[snr][rate] (see ga_rate_table)."""
+    import math
+    nr = len(rates)
+    snr_needed, ebno, flags = np.full(nr, np.nan), np.full(nr, np.nan), np.zeros(nr, np.int64)
+    start = 0
+    for r in range(nr):
+        idx, prev = None, None
+        for si in range(start, len(snr_vec)):
+            if bler[si, r] < target:
+                idx = si
+                break
+            prev = bler[si, r]
+        if idx is None:
+            flags[r] = 2
+            start = max(len(snr_vec) - 2, 0)
+            continue
+        if idx == start:
+            flags[r] = 1
+        else:
+            b = bler[idx, r]
+            snr_needed[r] = (snr_vec[idx] * math.log(prev / target) + snr_vec[idx - 1] * math.log(target / b)) / math.log(prev / b)
+            ebno[r] = snr_needed[r] - 10 * math.log10(rates[r]) - 10 * math.log10(nbits)
+        start = max(idx - 1, 0)
+    return snr_needed, ebno, flags

@@ -101,6 +101,31 @@ public:
             }
         return bler;
     }
+    // PolarM/PolarCode.m:198-255 ga_code_construction: in-place redesign by the Gaussian approximation on the GPU
+    // (polar_ga_construction). `constellation` = POLAR_CONST_* of include/polar_synth.h (| POLAR_RX_MLC for the MLC receiver); capacities computed
+    // by the library (integral for BPSK / MLC, 250 000-symbol polarized capacity of `seed` for multi-bit BICM). The frozen
+    // set is the K+crc most reliable channels, the info order the stable descending order; the CRC matrix is kept.
+    // Returns the BLER estimate (sum of qfunc(sqrt(c)/sqrt(2)) over the unfrozen channels); channels() holds the result.
+    double ga_code_construction(double design_snr_db, int constellation = 4 /* POLAR_CONST_BPSK */, double phi_dx = 1e-5,
+                                uint64_t seed = 1) {
+        const size_t N = _block_length, k = (size_t)_info_length + _crc_size;
+        std::vector<double> ch(N), pre(N);
+        std::vector<uint16_t> order(N);
+        check(polar_ga_construction(_n, constellation, &design_snr_db, 1, phi_dx, seed, nullptr, ch.data(), order.data(),
+                                    pre.data()));
+        std::vector<uint8_t> frozen(N, 1), crcm((size_t)_crc_size * _info_length);
+        for (size_t i = 0; i < k; ++i) frozen[order[i]] = 0;
+        if (_crc_size) check(polar_get_crc_matrix(_h, crcm.data()));
+        polar_code_t *h = nullptr;
+        const int rc = polar_create_explicit(_n, _info_length, _crc_size, frozen.data(), order.data(),
+                                             _crc_size ? crcm.data() : nullptr, &h);
+        check(rc);
+        polar_destroy(_h);
+        _h = h;
+        _channels = ch;
+        return pre[k - 1];
+    }
+    const std::vector<double> &channels() const { return _channels; }
     polar_code_t *handle() { return _h; }
 
 private:
@@ -113,6 +138,7 @@ private:
     polar_code_t *_h = nullptr;
     uint8_t _n;
     uint16_t _info_length, _block_length = 0, _crc_size;
+    std::vector<double> _channels;
 };
 
 #endif

@@ -179,3 +179,49 @@ hipError_t polar_launch_mlc_front(const PolarMlcParams &p, int mode, hipStream_t
 hipError_t polar_launch_mlc_sc(const PolarMlcParams &p, int grid, hipStream_t st);
 hipError_t polar_launch_mlc_sc_lat(const PolarMlcParams &p, int grid, hipStream_t st);
 hipError_t polar_launch_mlc_genie(const PolarMlcParams &p, int grid, hipStream_t st);
+
+// Gaussian-approximation code construction (polar_kernels_ga.hip; PolarM/PolarCode.m:198-255, GaussianApproximation/,
+// CapacityHelper/, Constellation.m:190-370). All fp64.
+// Capacity integrals: one block per (SNR, bit / layer) over the grid y_k = -ymax + k*dy, k = 0 .. P-1; per-thread sums
+// in k order, then a fixed LDS tree: the result depends on the grid alone.
+#define POLAR_GA_THREADS 256
+#define POLAR_GA_PHI_FWD 10002          // x = 0 : 0.01 : 100.01 (initialize_phi.m)
+#define POLAR_GA_PHI_INV 100001         // bins of -log(phi), width 1e-3 over [0, 100]
+#define POLAR_GA_BINS 801               // polarized capacity: u-LLR bins of width 0.25 over [-100, 100]
+struct PolarGaGrid {
+    double n0, ymax, dy;
+    long P;
+};
+struct PolarGaCapParams {
+    int kind;                    // 0 BICM (get_bicm_capacity), 1 MLC (get_mlc_capacity), 2 get_bpsk_cap
+    int nb, ns;
+    double pt[16];               // normalised constellation points, symbol index order
+    const PolarGaGrid *grid;     // [n_snr]
+    double *out;                 // [n_snr][nb] (kind 2: [n_snr])
+};
+hipError_t polar_launch_ga_capacity(const PolarGaCapParams &p, int n_snr, hipStream_t st);
+// phi tables: fwd [POLAR_GA_PHI_FWD] doubles; inv [POLAR_GA_PHI_INV] bit patterns of the largest x of each bin (0 = none),
+// x_k = k*dx for k = 0 .. nx-1
+hipError_t polar_launch_ga_phi(double *fwd, unsigned long long *inv, double dx, long nx, hipStream_t st);
+// polarized capacity: counts [n_snr][nb][POLAR_GA_BINS][2] (u-LLR bin, sent bit), ADDED to
+struct PolarGaPolParams {
+    int constellation, nb;
+    double cnorm;
+    const double *sigma, *n0;    // [n_snr]
+    uint64_t seed, trial0;
+    long num_sym;
+    unsigned long long *counts;
+};
+hipError_t polar_launch_ga_polarized(const PolarGaPolParams &p, int n_snr, hipStream_t st);
+// GA polarization + stable descending sort + BLER prefix sums, one block per design point
+struct PolarGaConsParams {
+    int m, M, nb, N;             // sub-block length M = 2^m = N / nb
+    const double *mean_llr;      // [n_points][nb]
+    const double *fwd;           // phi tables (see polar_launch_ga_phi)
+    const unsigned long long *inv;
+    double *scr;                 // [n_points][2][N]
+    double *channels;            // [n_points][N]
+    uint16_t *order;             // [n_points][N]
+    double *prefix;              // [n_points][N]
+};
+hipError_t polar_launch_ga_construct(const PolarGaConsParams &p, int n_points, hipStream_t st);

@@ -18,6 +18,7 @@ classdef PolarCode < handle
         cc_method        % 'bhattacharya' | 'monte-carlo' (as PolarM :89, :107)
         cc_parameter
         cc_misc
+        channels        % GA channel mean LLRs (ga_code_construction)
     end
     properties (Access = private)
         h                % uint64 handle owned by the MEX gateway
@@ -63,6 +64,30 @@ classdef PolarCode < handle
             obj.frozen_bits = double(fz);
             obj.info_bits = double(order0(1 : obj.info_length + obj.crc_size)) + 1;
             fprintf('Monte carlo code construction done. Bler estimate = %g\n', est);
+        end
+        function bler_estimate = ga_code_construction(obj, design_snr_db, constellation_name, receiver_algo, phi_dx, seed, capacity)
+            % ga_code_construction(design_snr_db, constellation_name, receiver_algo [, phi_dx, seed, capacity])
+            % Same method name and first arguments as the reference (PolarM/PolarCode.m:198); the design — capacities,
+            % Gaussian-approximation polarization, stable descending sort, BLER estimate and the new decoder handle — is ONE
+            % gateway call ('ga_design') on the GPU. `capacity` (1 x n_bits) replaces the computed capacities.
+            if nargin < 3, constellation_name = 'bpsk'; end
+            if nargin < 4, receiver_algo = 'bicm'; end
+            if nargin < 5, phi_dx = 1e-5; end
+            if nargin < 6, seed = 1; end
+            if nargin < 7, capacity = []; end
+            cid = find(strcmp(constellation_name, {'ask4-gray', 'ask8-gray', 'ask16-gray', 'bpsk', 'ask4-sp', 'ask8-sp', 'ask16-sp'}));   % POLAR_CONST_*
+            assert(~isempty(cid), 'unsupported constellation');
+            if strcmp(receiver_algo, 'mlc'), cid = cid + 256; end                                    % POLAR_RX_MLC
+            old = obj.h;
+            [obj.h, fz, order0, bler_estimate, channels] = polar_mex('ga_design', obj.n, obj.info_length, obj.crc_size, ...
+                uint8(obj.crc_matrix), cid, design_snr_db, phi_dx, seed, capacity);
+            polar_mex('destroy', old);
+            obj.frozen_bits = double(fz);
+            obj.info_bits = double(order0(1 : obj.info_length + obj.crc_size)) + 1;
+            obj.channels = channels;
+            [obj.cc_method, obj.cc_parameter] = deal('gauss-approx', design_snr_db);
+            obj.cc_misc = [constellation_name, '_', receiver_algo];
+            disp(['GA code construction done. BLER estimate:', num2str(bler_estimate)]);
         end
         function unique_string = get_unique_string(obj)                % PolarM :258-261
             unique_string = [num2str(obj.block_length), '_', num2str(length(obj.info_bits)), ...

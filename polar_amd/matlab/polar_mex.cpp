@@ -137,6 +137,46 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(est / (double)runs);
         return;
     }
+    if (c == "ga_design") {
+        // [h, frozen, order0, bler_est, channels] = polar_mex('ga_design', n, K, crc, crc_matrix, constellation_id,
+        //                                                     design_snr_db, phi_dx, seed [, capacity])
+        // PolarM/PolarCode.m:198-255 in one call: GA construction on the GPU (polar_ga_construction; constellation_id may
+        // carry POLAR_RX_MLC), frozen set = the K+crc most reliable channels, order = stable descending order of the
+        // channels, explicit-table handle. `capacity` (1 x n_bits doubles) replaces the computed capacities.
+        need(nrhs, 9, "'ga_design', n, K, crc, crc_matrix, constellation_id, design_snr_db, phi_dx, seed [, capacity]");
+        const int n_ = (int)mxGetScalar(prhs[1]), K_ = (int)mxGetScalar(prhs[2]), crc_ = (int)mxGetScalar(prhs[3]);
+        if (n_ < 1 || n_ > POLAR_MAX_N_LOG2 || K_ < 1 || crc_ < 0 || (size_t)(K_ + crc_) > ((size_t)1 << n_)) mexErrMsgIdAndTxt("polar_amd:size", "bad n / K / crc");
+        if (crc_ > 0) want_class(prhs[4], mxUINT8_CLASS, (size_t)crc_ * K_, "crc_matrix (uint8, crc x K)");
+        const int cid = (int)mxGetScalar(prhs[5]);
+        const double snr = mxGetScalar(prhs[6]);
+        const double *cap = nullptr;
+        if (nrhs > 9 && mxGetNumberOfElements(prhs[9]) > 0) {
+            static const int nbits[8] = {1, 2, 3, 4, 1, 2, 3, 4};              // POLAR_CONST_* ids 1..7 (include/polar_synth.h)
+            const int id = cid & ~POLAR_RX_MLC;
+            want_class(prhs[9], mxDOUBLE_CLASS, (size_t)(id >= 1 && id <= 7 ? nbits[id] : 1), "capacity (double, 1 x n_bits)");
+            cap = mxGetPr(prhs[9]);
+        }
+        const size_t N_ = (size_t)1 << n_;
+        std::vector<double> ch(N_), pre(N_);
+        std::vector<uint16_t> order(N_);
+        check(polar_ga_construction(n_, cid, &snr, 1, mxGetScalar(prhs[7]), (uint64_t)mxGetScalar(prhs[8]), cap, ch.data(),
+                                    order.data(), pre.data()));
+        std::vector<uint8_t> frozen(N_, 1), m((size_t)crc_ * K_);
+        for (int i = 0; i < K_ + crc_; ++i) frozen[order[i]] = 0;
+        if (crc_ > 0) {
+            const uint8_t *d = (const uint8_t *)mxGetData(prhs[4]);           // column-major crc x K
+            for (int i = 0; i < crc_; ++i)
+                for (int j = 0; j < K_; ++j) m[(size_t)i * K_ + j] = d[(size_t)j * crc_ + i];
+        }
+        polar_code_t *h = nullptr;
+        check(polar_create_explicit(n_, K_, crc_, frozen.data(), order.data(), crc_ > 0 ? m.data() : nullptr, &h));
+        plhs[0] = new_handle(h);
+        if (nlhs > 1) { plhs[1] = mxCreateNumericMatrix(1, N_, mxUINT8_CLASS, mxREAL); memcpy(mxGetData(plhs[1]), frozen.data(), N_); }
+        if (nlhs > 2) { plhs[2] = mxCreateNumericMatrix(1, N_, mxUINT16_CLASS, mxREAL); memcpy(mxGetData(plhs[2]), order.data(), 2 * N_); }
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(pre[K_ + crc_ - 1]);
+        if (nlhs > 4) { plhs[4] = mxCreateDoubleMatrix(1, N_, mxREAL); memcpy(mxGetPr(plhs[4]), ch.data(), 8 * N_); }
+        return;
+    }
     need(nrhs, 2, "cmd, handle, ...");
     polar_code_t *h = H(prhs[1]);
     int n, N, K, crc;
