@@ -230,6 +230,41 @@ int polar_mc_batch_bicm(polar_code_t *h, int constellation, uint64_t seed, uint6
                         const double *snr_db, int n_s, const uint8_t *L, int n_L,
                         const uint8_t *enabled, uint64_t *err, uint64_t *run);
 
+/* ---- the Constellation class beside PolarCode (PolarM/Constellation.m) and the symbol-domain BICM receiver ----
+ * `constellation` is a POLAR_CONST_* id 1 .. 7 (include/polar_synth.h: BPSK, 4- / 8- / 16-ASK with Gray or set-partition labels),
+ * nb its bits per symbol, M = floor(N / nb) symbols per row of N coded bits.
+ *   polar_modulate        Constellation.modulate (:84-93, symbol index = sum 2^j bit_j, LSB first) on the host: coded [B][N]
+ *                         -> normalised points sym [B][M]; the N - M*nb tail bits of a row are not sent. No handle, no device.
+ *   polar_demap_bicm      Constellation.compute_llr_bicm (:123-144) on the device: y [B][M] with noise variance n0 -> llr [B][N]
+ *                         and / or p1 [B][N] (either may be NULL, not both), position i*nb + j = label bit j of symbol i, the
+ *                         tail positions M*nb .. N-1 llr = 0, p1 = 0.5 (main_MC_CC_Comparison.m:94). Every value is bit for bit
+ *                         polar_synth_bicm_demap2 of include/polar_synth.h (fixed-order exp / log, the same on host and device).
+ *                         Host pointers, no handle; _dev: device pointers, asynchronous on `stream`; _f32: single-precision
+ *                         symbols, each widened exactly.
+ *   polar_decode_bicm_batch   decode_scl_llr from received symbols: the result is bit for bit polar_decode_scl_llr_batch on
+ *                         polar_demap_bicm's LLRs of the same y (for _f32: of (double)y[i]), from 1 / nb (double) or 1 / 2nb
+ *                         (float) of the input bytes. Host pointers: the staging, pipelining and latency paths of
+ *                         polar_decode_scl_llr_batch, chosen for a given B as that function chooses them, with the symbols
+ *                         demapped on the device in front of the decode. _dev: device pointers, stream-ordered, no host
+ *                         synchronisation (the handle's LLR buffer is grown on demand like its other scratch); d_pm as
+ *                         polar_decode_scl_llr_batch_dev.
+ *   polar_synth_bicm_sym_dev  the received symbols [B][M] of the trials for which polar_synth_bicm_llr_dev gives the LLRs.
+ * POLAR_E_ARG: NULL pointers, constellation 0 or unknown, n0 not finite or <= 0, L out of range, negative B, N outside
+ * [1, 2^POLAR_MAX_N_LOG2]; B = 0 is POLAR_OK. */
+int polar_modulate(int constellation, const uint8_t *coded, int N, long B, double *sym);
+int polar_demap_bicm(int constellation, const double *y, int N, long B, double n0, double *llr, double *p1);
+int polar_demap_bicm_f32(int constellation, const float *y, int N, long B, double n0, double *llr, double *p1);
+int polar_demap_bicm_dev(int constellation, const double *d_y, int N, long B, double n0, double *d_llr, double *d_p1, void *stream);
+int polar_demap_bicm_dev_f32(int constellation, const float *d_y, int N, long B, double n0, double *d_llr, double *d_p1, void *stream);
+int polar_decode_bicm_batch(polar_code_t *h, int constellation, const double *y, double n0, long B, int L, uint8_t *out);
+int polar_decode_bicm_batch_f32(polar_code_t *h, int constellation, const float *y, double n0, long B, int L, uint8_t *out);
+int polar_decode_bicm_batch_dev(polar_code_t *h, int constellation, const double *d_y, double n0, long B, int L, uint8_t *d_out,
+                                double *d_pm, void *stream);
+int polar_decode_bicm_batch_dev_f32(polar_code_t *h, int constellation, const float *d_y, double n0, long B, int L, uint8_t *d_out,
+                                    double *d_pm, void *stream);
+int polar_synth_bicm_sym_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double snr_db,
+                             double *d_y, uint8_t *d_info, void *stream);
+
 /* ---- Monte-Carlo code construction (PolarM/PolarCode.m:143-196 `monte_carlo`, receiver 'bicm',
  * with the genie-aided SC decoder `polar_decode_monte` :897-914). No handle: the result is what a
  * code is built FROM. For runs trial0 .. trial0+num_runs-1 (counter-based inputs, polar_synth.h):

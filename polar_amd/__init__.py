@@ -109,6 +109,61 @@ def _stream_ptr(stream):
     return C.c_void_p(int(stream))
 
 
+class Constellation:
+    """The reference's ``Constellation`` (PolarM/Constellation.m) over the C-ABI: ``Constellation("ask16-gray")`` has ``name``,
+    ``n_bits``, ``n_sym``, ``points`` (normalised to unit mean energy, in symbol-index order, :19-32, 80), ``modulate`` (:84-93,
+    on the host) and ``compute_llr_bicm`` (:123-144, on the GPU: there is no CPU path)."""
+
+    def __init__(self, name):
+        self.id = _constellation_id(name)
+        if self.id not in _NBITS:
+            raise PolarError(f"unknown constellation {name!r} (supported: {sorted(CONSTELLATION_NAMES)})")
+        self.name = name if isinstance(name, str) else {v: k for k, v in CONSTELLATION_NAMES.items()}[self.id]
+        self.n_bits = _NBITS[self.id]
+        self.n_sym = 1 << self.n_bits
+        # symbol s is what the bits of s (LSB first) modulate to
+        labels = ((np.arange(self.n_sym)[:, None] >> np.arange(self.n_bits)[None, :]) & 1).astype(np.uint8)
+        self.points = self.modulate(labels.reshape(-1))
+
+    def modulate(self, bits):
+        """bits [N] or [B][N] (0 / 1) -> symbols [floor(N / n_bits)] or [B][...]: symbol index = sum 2^j * bit j, LSB first."""
+        a = np.ascontiguousarray(bits, np.uint8)
+        if a.ndim not in (1, 2) or a.shape[-1] < 1:
+            raise PolarError(f"modulate: bits must be [N] or [B][N], got shape {a.shape}")
+        single = a.ndim == 1
+        a2 = a.reshape(1, -1) if single else a
+        out = np.zeros((a2.shape[0], a2.shape[1] // self.n_bits), np.float64)
+        _check(lib().polar_modulate(C.c_int(self.id), _p(a2, _u8p), C.c_int(a2.shape[1]), C.c_long(a2.shape[0]), _p(out, _dp)))
+        return out[0] if single else out
+
+    def compute_llr_bicm(self, y, n0, block_length=None):
+        """Constellation.compute_llr_bicm: (p1, llr) in the reference's output order, interleaved (position i*n_bits + j =
+        label bit j of symbol i). y is [M] or [B][M], float64 or float32 (widened exactly on the device). ``block_length`` N
+        (default M * n_bits) pads every row to N positions, the tail with llr = 0 / p1 = 0.5 (main_MC_CC_Comparison.m:94)."""
+        f32 = isinstance(y, np.ndarray) and y.dtype == np.float32
+        a = np.ascontiguousarray(y) if f32 else np.ascontiguousarray(y, np.float64)
+        if a.ndim not in (1, 2):
+            raise PolarError(f"compute_llr_bicm: y must be [M] or [B][M], got shape {a.shape}")
+        single = a.ndim == 1
+        a2 = a.reshape(1, -1) if single else a
+        B, M = a2.shape
+        N = M * self.n_bits if block_length is None else int(block_length)
+        if N < 1 or N // self.n_bits != M:
+            raise PolarError(f"compute_llr_bicm: rows of {M} symbols do not make rows of {N} positions at {self.n_bits} bits per symbol")
+        p1, llr = np.zeros((B, N)), np.zeros((B, N))
+        f = lib().polar_demap_bicm_f32 if f32 else lib().polar_demap_bicm
+        _check(f(C.c_int(self.id), _p(a2, C.POINTER(C.c_float) if f32 else _dp), C.c_int(N), C.c_long(B), C.c_double(n0),
+                 _p(llr, _dp), _p(p1, _dp)))
+        return (p1[0], llr[0]) if single else (p1, llr)
+
+    def compute_llr_bicm_dev(self, y_ptr, block_length, B, n0, llr_ptr=0, p1_ptr=0, stream=None, f32=False):
+        """Device-resident form: y [B][block_length // n_bits] (float64, or float32 with f32=True) -> llr and / or p1
+        [B][block_length] doubles (a pointer of 0 leaves that output out); asynchronous on `stream`."""
+        f = lib().polar_demap_bicm_dev_f32 if f32 else lib().polar_demap_bicm_dev
+        _check(f(C.c_int(self.id), C.c_void_p(y_ptr), C.c_int(block_length), C.c_long(B), C.c_double(n0),
+                 C.c_void_p(llr_ptr), C.c_void_p(p1_ptr), _stream_ptr(stream)))
+
+
 class PolarCode:
     """Drop-in for the reference ``PolarCode``.
 
@@ -433,6 +488,47 @@ class PolarCode:
         self._chk(self._L.polar_synth_mlc_dev(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed),
                                               C.c_uint64(trial0), C.c_long(B), C.c_double(snr_db), C.c_void_p(y_ptr),
                                               C.c_void_p(info_ptr), _stream_ptr(stream)))
+
+    # ---- symbol-domain BICM receiver (Constellation.m:123-144 in front of decode_scl_llr) ---------
+    def decode_bicm(self, y, n0, constellation, list_size, out=None):
+        """decode_scl_llr from received symbols y [B][M] (or [M]), M = N // n_bits, with noise variance n0: bit for bit
+        ``decode_scl_llr(Constellation(c).compute_llr_bicm(y, n0, N)[1], list_size)`` from 1 / n_bits of the input bytes —
+        1 / (2 n_bits) for float32 symbols, which are widened exactly on the device. ``out`` as decode_scl_llr's."""
+        cid = constellation.id if isinstance(constellation, Constellation) else _constellation_id(constellation)
+        f32 = isinstance(y, np.ndarray) and y.dtype == np.float32
+        a = np.ascontiguousarray(y) if f32 else np.ascontiguousarray(y, np.float64)
+        single = a.ndim == 1
+        nb = _NBITS.get(cid, 0)
+        if nb:
+            # (the library copies B * M elements from the caller's rows: a row of any other width is refused here; an unknown
+            # constellation is refused by the library before it reads anything)
+            M = self.N // nb
+            if a.ndim not in (1, 2) or a.shape[-1] != M:
+                raise PolarError(f"decode_bicm: y must be [B][{M}] or [{M}] (M = N // n_bits = {self.N} // {nb}), got shape {a.shape}")
+        a2 = a.reshape(1, -1) if single else a
+        B = a2.shape[0]
+        if out is None:
+            out = np.zeros((B, self.K), np.uint8)
+        elif out.dtype != np.uint8 or out.shape != (B, self.K) or not out.flags.c_contiguous:
+            raise PolarError("out must be a C-contiguous uint8 array of shape [B, K]")
+        f = self._L.polar_decode_bicm_batch_f32 if f32 else self._L.polar_decode_bicm_batch
+        self._chk(f(self._h, C.c_int(cid), _p(a2, C.POINTER(C.c_float) if f32 else _dp), C.c_double(n0), C.c_long(B),
+                    C.c_int(list_size), _p(out, _u8p)))
+        return out[0] if single else out
+
+    def decode_bicm_dev(self, constellation, y_ptr, n0, B, list_size, out_ptr, pm_ptr=0, stream=None, f32=False):
+        """Device-resident symbols [B][N // n_bits] (float64, or float32 with f32=True) -> uint8 [B][K]; asynchronous on
+        `stream`, path metrics as decode_scl_llr_dev."""
+        cid = constellation.id if isinstance(constellation, Constellation) else _constellation_id(constellation)
+        f = self._L.polar_decode_bicm_batch_dev_f32 if f32 else self._L.polar_decode_bicm_batch_dev
+        self._chk(f(self._h, C.c_int(cid), C.c_void_p(y_ptr), C.c_double(n0), C.c_long(B), C.c_int(list_size),
+                    C.c_void_p(out_ptr), C.c_void_p(pm_ptr), _stream_ptr(stream)))
+
+    def synth_bicm_sym_dev(self, constellation, seed, trial0, B, snr_db, y_ptr, info_ptr=0, stream=None):
+        """The received symbols [B][N // n_bits] of the trials synth_bicm_llr_dev gives the LLRs of."""
+        self._chk(self._L.polar_synth_bicm_sym_dev(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed),
+                                                   C.c_uint64(trial0), C.c_long(B), C.c_double(snr_db), C.c_void_p(y_ptr),
+                                                   C.c_void_p(info_ptr), _stream_ptr(stream)))
 
     # names used by BASELINE.json's north_star
     decode_SCL_LLR = decode_scl_llr

@@ -76,6 +76,29 @@ public:
         check(polar_decode_scl_llr_batch_f32(_h, llr.data(), B, list_size, out.data()));
         return out;
     }
+    // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
+    // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
+    // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").
+    // One codeword, or B codewords back to back (doubles or floats: a float is widened exactly on the device).
+    std::vector<uint8_t> decode_bicm(const std::vector<double> &y, double n0, const std::string &constellation_name, uint16_t list_size) {
+        const long B = bicm_rows(y.size(), constellation_name);
+        std::vector<uint8_t> out((size_t)B * _info_length);
+        check(polar_decode_bicm_batch(_h, constellation_id(constellation_name), y.data(), n0, B, list_size, out.data()));
+        return out;
+    }
+    std::vector<uint8_t> decode_bicm(const std::vector<float> &y, double n0, const std::string &constellation_name, uint16_t list_size) {
+        const long B = bicm_rows(y.size(), constellation_name);
+        std::vector<uint8_t> out((size_t)B * _info_length);
+        check(polar_decode_bicm_batch_f32(_h, constellation_id(constellation_name), y.data(), n0, B, list_size, out.data()));
+        return out;
+    }
+    // POLAR_CONST_* of include/polar_synth.h by the reference's constellation name (Constellation.m:41-66)
+    static int constellation_id(const std::string &name) {
+        static const char *const names[] = {"", "ask4-gray", "ask8-gray", "ask16-gray", "bpsk", "ask4-sp", "ask8-sp", "ask16-sp"};
+        for (int i = 1; i < 8; ++i)
+            if (name == names[i]) return i;
+        throw std::out_of_range("unknown constellation " + name);
+    }
 
     // PolarCode.cpp:658: bler[list_index][ebno_index]; reference constants max_err=100, max_runs=1000
     // PolarCode.h:32-34. `devices` (optional): shard the trials of every round over these GPUs of the node
@@ -134,6 +157,12 @@ private:
     }
     static void need(bool ok, const char *msg) {
         if (!ok) throw std::out_of_range(msg);   // the reference throws out_of_range from .at()
+    }
+    long bicm_rows(size_t n_sym, const std::string &name) const {
+        const int id = constellation_id(name);
+        const size_t M = _block_length / (size_t)(id == 4 ? 1 : id == 1 || id == 5 ? 2 : id == 2 || id == 6 ? 3 : 4);
+        need(M > 0 && n_sym % M == 0, "decode_bicm: size must be a multiple of block_length / n_bits");
+        return (long)(n_sym / M);
     }
     polar_code_t *_h = nullptr;
     uint8_t _n;

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "polar_kernels.h"
 #include "polar_synth.h"
 
@@ -83,13 +85,16 @@ __global__ __launch_bounds__(64) void synth_kernel(PolarEncodeParams p) {
             // ASK Gray + BICM demapper: Constellation.m:84-93, 123-144 (include/polar_synth.h)
             const int nb = polar_const_nbits(p.constellation);
             const int nsym = p.N / nb;
-            double *dl = p.llr + (size_t)b * p.N;
-            for (int i = nsym * nb + lane; i < p.N; i += 64) dl[i] = 0.0;
+            double *dl = p.llr ? p.llr + (size_t)b * p.N : nullptr;
+            if (dl)
+                for (int i = nsym * nb + lane; i < p.N; i += 64) dl[i] = 0.0;
             for (int i = lane; i < nsym; i += 64) {
                 int sym = 0;
                 for (int j = 0; j < nb; ++j) sym += (1 << j) * (int)u[__brev((unsigned)(i * nb + j)) >> (32 - p.n)];
                 const double x = polar_const_point(p.constellation, sym) / p.cnorm;
                 const double y = x + polar_synth_symbol_noise(p.seed, trial, (uint32_t)i) * p.sigma;
+                if (p.y_out) p.y_out[(size_t)b * nsym + i] = y;
+                if (!dl) continue;
                 double l4[4];
                 polar_synth_bicm_demap(p.constellation, p.cnorm, y, p.n0, l4);
                 for (int j = 0; j < nb; ++j) dl[(size_t)i * nb + j] = l4[j];
@@ -109,6 +114,89 @@ __global__ __launch_bounds__(64) void synth_kernel(PolarEncodeParams p) {
             dst[pr] = v;
         }
         wave_sync();
+    }
+}
+
+// ---- the BICM demapper on its own (Constellation.m:123-144): received symbols -> interleaved LLR / p1 rows ----
+// One lane per symbol, 256 symbols of a row per block, rows grid-strided over blockIdx.y. Per symbol 2^NB exponentials in
+// symbol-index order and NB logarithms / divisions, all fp64 VALU work in registers (both loops unrolled: the label bit of
+// (symbol, level) is a compile-time constant); the arithmetic is polar_synth_bicm_demap2's term for term — the same sums in
+// the same order — with the normalised points taken from the launch parameters (computed once by the host with the same
+// two correctly rounded operations). The loads are coalesced (consecutive lanes, consecutive symbols); the NB outputs of a
+// lane are contiguous: 16-byte stores for 2 and 4 bits when the rows are 16-byte aligned (VEC), else one double per store
+// (3 bits: 24 contiguous bytes per lane either way).
+// one symbol: polar_synth_bicm_demap2 with the points given and the loops over a compile-time n_bits
+template <int NB>
+__host__ __device__ __forceinline__ void demap_symbol(const double *pt, double y, double n0, bool want_llr, double *l, double *q) {
+    constexpr int NS = 1 << NB;
+    double p0[NB], p1[NB];
+#pragma unroll
+    for (int m = 0; m < NB; ++m) { p0[m] = 0; p1[m] = 0; }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        double d = y - pt[s];
+        double ad = d < 0 ? -d : d;
+        double ps = polar_synth_exp_neg(-(ad * ad) / 2 / n0);
+#pragma unroll
+        for (int m = 0; m < NB; ++m) {
+            if (((s >> m) & 1) == 0) p0[m] = p0[m] + ps; else p1[m] = p1[m] + ps;
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < NB; ++m) {
+        l[m] = want_llr ? polar_synth_log(p0[m] / p1[m]) : 0.0;
+        q[m] = p1[m] / (p0[m] + p1[m]);
+    }
+}
+
+template <int NB, typename T, bool VEC>
+__global__ __launch_bounds__(256) void bicm_demap_kernel(PolarDemapParams p) {
+    const long Bv = p.n_dev ? ((long)*p.n_dev < p.B ? (long)*p.n_dev : p.B) : p.B;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int tail = p.M * NB + (int)threadIdx.x;          // (N - M * NB < NB positions)
+    const T *ys = static_cast<const T *>(p.y);
+    for (long b = blockIdx.y; b < Bv; b += gridDim.y) {
+        double *dl = p.llr ? p.llr + (size_t)b * p.N : nullptr;
+        double *dp = p.p1 ? p.p1 + (size_t)b * p.N : nullptr;
+        if (blockIdx.x == 0 && tail < p.N) {               // unused tail positions: p1 = 0.5 <=> llr = 0 (main_MC_CC_Comparison.m:94)
+            if (dl) dl[tail] = 0.0;
+            if (dp) dp[tail] = 0.5;
+        }
+        if (i >= p.M) continue;
+        const double y = (double)ys[(size_t)b * p.M + i];  // (float -> double is exact)
+        double l[NB], q[NB];
+        demap_symbol<NB>(p.pt, y, p.n0, dl != nullptr, l, q);
+        const size_t o = (size_t)i * NB;
+        if constexpr (VEC && (NB == 2 || NB == 4)) {
+#pragma unroll
+            for (int m = 0; m < NB; m += 2) {
+                if (dl) *reinterpret_cast<double2 *>(dl + o + m) = make_double2(l[m], l[m + 1]);
+                if (dp) *reinterpret_cast<double2 *>(dp + o + m) = make_double2(q[m], q[m + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < NB; ++m) {
+                if (dl) dl[o + m] = l[m];
+                if (dp) dp[o + m] = q[m];
+            }
+        }
+    }
+}
+
+template <int NB, typename T>
+hipError_t launch_demap_nb(const PolarDemapParams &p, dim3 grid, bool vec, hipStream_t st) {
+    if (vec) hipLaunchKernelGGL((bicm_demap_kernel<NB, T, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((bicm_demap_kernel<NB, T, false>), grid, dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_demap(const PolarDemapParams &p, dim3 grid, bool vec, hipStream_t st) {
+    switch (p.nb) {
+        case 1: return launch_demap_nb<1, T>(p, grid, false, st);
+        case 2: return launch_demap_nb<2, T>(p, grid, vec, st);
+        case 3: return launch_demap_nb<3, T>(p, grid, false, st);
+        case 4: return launch_demap_nb<4, T>(p, grid, vec, st);
+        default: return hipErrorInvalidValue;
     }
 }
 
@@ -160,6 +248,14 @@ hipError_t polar_launch_encode(const PolarEncodeParams &p, hipStream_t st) {
 hipError_t polar_launch_synth(const PolarEncodeParams &p, hipStream_t st) {
     hipLaunchKernelGGL(synth_kernel, dim3(grid_for(p.B)), dim3(64), (size_t)p.N + p.K, st, p);
     return hipGetLastError();
+}
+hipError_t polar_launch_bicm_demap(const PolarDemapParams &p, hipStream_t st) {
+    if (p.nb < 1 || p.nb > 4 || p.M != p.N / p.nb || (!p.llr && !p.p1) || !p.y) return hipErrorInvalidValue;
+    if (p.B <= 0) return hipSuccess;
+    // (a row starts 16-byte aligned when the base is and N is even; symbol i of a 2- / 4-bit label then starts at a multiple of 16 bytes)
+    const bool vec = (((uintptr_t)p.llr | (uintptr_t)p.p1) & 15u) == 0 && (p.N & 1) == 0;
+    const dim3 grid((unsigned)std::max(1, (p.M + 255) / 256), (unsigned)grid_for(p.B));
+    return p.y_f32 ? launch_demap<float>(p, grid, vec, st) : launch_demap<double>(p, grid, vec, st);
 }
 hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T, hipStream_t st) {
     const long blocks = (T + 255) / 256;

@@ -4,6 +4,7 @@
 //   polar_handle.cpp      construction (the reference's constructor work), tables, device upload, getters / setters
 //   polar_decode.cpp      kernel-family dispatch of decode_scl_llr (decode_impl), device-resident entry points, P1 paths, encoder
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
+//   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the pipelined-round scheduler, Monte-Carlo code construction
 //   polar_multi.cpp       multi-device context: RCCL binding, worker threads, watchdog, per-device clones
 //   polar_debug.cpp       measurement knobs (include/polar_amd_debug.h); fault injection only with -DPOLAR_TEST_HOOKS
@@ -252,6 +253,7 @@ struct polar_code {
     DevBuf<uint8_t> d_flags;
     DevBuf<uint32_t> d_list;
     DevBuf<unsigned int> d_count;
+    DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never
     // calls getenv. The fault-injection and device-sharing hooks have no environment form at all: polar_debug_set() only.
@@ -347,7 +349,15 @@ int mlc_check(const polar_code *h, int constellation, int *cid);
 void fill_mlc(const polar_code *h, int cid, double snr_db, PolarMlcParams &p);   // snr_db: sigma / n0 of the sweep's axis
 int mlc_decode_launch(polar_code *h, int cid, const double *d_y, double n0, long B, const unsigned int *n_dev, double *d_out,
                       uint8_t *d_out_bytes, hipStream_t st);
+// polar_bicm.cpp — symbol-domain BICM receiver
+int bicm_check(int constellation, double n0);             // POLAR_E_ARG for an unknown id or an n0 that is not finite and > 0
+void fill_demap(int cid, int N, double n0, PolarDemapParams &p);
+// demap B rows of symbols on `st` into the context's own LLR buffer (grown on demand): *d_llr = what decode_impl reads
+int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, long B, hipStream_t st, const double **d_llr);
 // polar_hostpipe.cpp
+// rows that are received symbols instead of LLRs (polar_decode_bicm_batch*): M elements per row, demapped on the device
+struct SymRows { int cid, M; double n0; };
+int host_decode(polar_code *h, const void *rows, int rows_f32, const SymRows *sym, long B, int L, uint8_t *out);
 void hostpipe_release(polar_code *h);
 // polar_multi.cpp
 void multi_release(polar_code *h, bool abort_comms);

@@ -109,12 +109,12 @@ static int hostpipe_ensure(polar_code_t *h, size_t in_slot, size_t out_slot, int
 
 // *no_staging is set when the call failed BEFORE anything was decoded because the staging slots / decode lanes could not be set
 // up (host_decode then takes the unpipelined path)
-static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, long B, int L, uint8_t *out, long chunk_cw, int lanes, int threads, bool ramp, bool *no_staging) {
+static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, const SymRows *sym, long B, int L, uint8_t *out, long chunk_cw, int lanes, int threads, bool ramp, bool *no_staging) {
     using clk = std::chrono::steady_clock;
     auto us = [](clk::time_point a, clk::time_point b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
     const clk::time_point t_begin = clk::now();
     const size_t esz = llr_f32 ? sizeof(float) : sizeof(double);
-    const size_t row_in = (size_t)h->N * esz, row_out = (size_t)h->K;
+    const size_t row_in = (size_t)(sym ? sym->M : h->N) * esz, row_out = (size_t)h->K;          // (symbol rows: M elements, demapped on the lane)
     // The chunks. A launch of the list kernels takes milliseconds whatever it carries (the N-step chain of one wave), so
     // (a) the first chunks are SMALL — an eighth of the full size, doubling: the device starts a fraction of a millisecond
     // after the call instead of after the first 128 MiB — and (b) the full-size chunks are equal (a short last one would be
@@ -167,7 +167,15 @@ static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, 
         hipStream_t st = hp->lane[l];
         if (e == hipSuccess) e = hipStreamWaitEvent(st, hp->h2d[slot], 0);
         if (e != hipSuccess) { rc = fail(POLAR_E_DEVICE, "host pipeline: copy of chunk %ld: %s", k, hipGetErrorString(e)); break; }
-        if ((rc = decode_impl(l ? hp->ctx[l] : h, hp->d_in[slot], llr_f32, nb, nullptr, L, hp->d_out[slot], nullptr, st, nullptr, nullptr))) break;
+        polar_code *c = l ? hp->ctx[l] : h;
+        const void *d_rows = hp->d_in[slot];
+        int rows_f32 = llr_f32;
+        if (sym) {          // the demap launch precedes the decode on the lane's stream; each lane's context owns its LLR rows
+            const double *d_llr = nullptr;
+            if ((rc = bicm_front(c, sym->cid, sym->n0, d_rows, llr_f32, nb, st, &d_llr))) break;
+            d_rows = d_llr; rows_f32 = 0;
+        }
+        if ((rc = decode_impl(c, d_rows, rows_f32, nb, nullptr, L, hp->d_out[slot], nullptr, st, nullptr, nullptr))) break;
         e = hipMemcpyAsync(hp->pin_out[slot], hp->d_out[slot], (size_t)nb * row_out, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipEventRecord(hp->done[slot], st);
         if (e != hipSuccess) { rc = fail(POLAR_E_DEVICE, "host pipeline: result copy of chunk %ld: %s", k, hipGetErrorString(e)); break; }
@@ -179,7 +187,7 @@ static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, 
     return POLAR_OK;
 }
 
-static int host_decode(polar_code_t *h, const void *llr, int llr_f32, long B, int L, uint8_t *out) {
+int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const SymRows *sym, long B, int L, uint8_t *out) {
     if (!h || !llr || !out) return fail(POLAR_E_ARG, "NULL argument");
     if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
     if (B < 0) return fail(POLAR_E_ARG, "negative batch");
@@ -187,8 +195,12 @@ static int host_decode(polar_code_t *h, const void *llr, int llr_f32, long B, in
     DevGuard dg_;
     int rc = ensure_device(h, dg_);
     if (rc) return rc;
-    const size_t esz = llr_f32 ? sizeof(float) : sizeof(double);
+    // Symbol rows: the thresholds and chunk sizes below were fitted to LLR bytes, so they are applied to the LLR bytes the symbols
+    // stand for (B * N doubles): a batch takes the form — zero-copy, one copy, pipelined, and the same chunks — that the LLR path
+    // takes for this B. They were not re-measured for the narrower rows.
+    const size_t esz = sym ? sizeof(double) : (llr_f32 ? sizeof(float) : sizeof(double));
     const size_t in_bytes = (size_t)B * h->N * esz, out_bytes = (size_t)B * h->K;
+    const size_t copy_bytes = sym ? (size_t)B * sym->M * (llr_f32 ? sizeof(float) : sizeof(double)) : in_bytes;          // what travels
     const int mode = h->knobs.mode_override >= 0 ? h->knobs.mode_override : h->mode;
     if (h->hpipe) h->hpipe->last_chunks = 0;
     {
@@ -226,7 +238,7 @@ static int host_decode(polar_code_t *h, const void *llr, int llr_f32, long B, in
             const int threads = kn.host_threads > 0 ? (int)std::min<long>(kn.host_threads, 64) : std::max(1, std::min(8, usable_cpus() / 2));
             if (B > chunk_cw) {
                 bool no_staging = false;
-                rc = host_decode_pipelined(h, llr, llr_f32, B, L, out, chunk_cw, lanes, threads, ramp, &no_staging);
+                rc = host_decode_pipelined(h, llr, llr_f32, sym, B, L, out, chunk_cw, lanes, threads, ramp, &no_staging);
                 // (no staging memory: the batch is decoded by the unpipelined path below, as round 4 decoded every batch)
                 if (!no_staging) return rc;
                 if (h->hpipe) h->hpipe->last_chunks = -1;          // (polar_debug_get "host_chunks" = -1: the fallback was taken)
@@ -250,27 +262,44 @@ static int host_decode(polar_code_t *h, const void *llr, int llr_f32, long B, in
             HIP_TRY(hipHostGetDevicePointer((void **)&h->pin_out_dev, h->pin_out, 0));
             h->pin_out_cap = cap;
         }
-        memcpy(h->pin_in, llr, in_bytes);
+        memcpy(h->pin_in, llr, copy_bytes);
+        const void *d_rows = h->pin_in_dev;
+        int rows_f32 = llr_f32;
+        if (sym) {          // demap first (the kernel reads the mapped symbols), then the latency kernel on the LLR rows in HBM
+            const double *d_llr = nullptr;
+            if ((rc = bicm_front(h, sym->cid, sym->n0, d_rows, llr_f32, B, nullptr, &d_llr))) return rc;
+            d_rows = d_llr; rows_f32 = 0;
+        }
         int deferred = 0;
         h->lat_flag_bytes = h->pin_out_dev + out_bytes;
-        rc = decode_impl(h, h->pin_in_dev, llr_f32, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 1, &deferred);
+        rc = decode_impl(h, d_rows, rows_f32, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 1, &deferred);
         h->lat_flag_bytes = nullptr;
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));
         bool any = !deferred;
         for (long i = 0; i < B && !any; ++i) any = h->pin_out[out_bytes + i] != 0;
         if (any && deferred) {
-            if ((rc = decode_impl(h, h->pin_in_dev, llr_f32, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
+            if ((rc = decode_impl(h, d_rows, rows_f32, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
             HIP_TRY(hipStreamSynchronize(nullptr));
         }
         memcpy(out, h->pin_out, out_bytes);
         return POLAR_OK;
     }
-    void *d_in;
-    if (llr_f32) { if ((rc = h->d_f32.ensure((size_t)B * h->N))) return rc; d_in = h->d_f32.p; }
-    else { if ((rc = h->d_in.ensure((size_t)B * h->N))) return rc; d_in = h->d_in.p; }
-    if ((rc = h->d_out.ensure(out_bytes))) return rc;
-    HIP_TRY(hipMemcpy(d_in, llr, in_bytes, hipMemcpyHostToDevice));
+    const void *d_in;
+    {
+        const size_t n_in = (size_t)B * (sym ? sym->M : h->N);
+        void *d_stage;
+        if (llr_f32) { if ((rc = h->d_f32.ensure(n_in))) return rc; d_stage = h->d_f32.p; }
+        else { if ((rc = h->d_in.ensure(n_in))) return rc; d_stage = h->d_in.p; }
+        if ((rc = h->d_out.ensure(out_bytes))) return rc;
+        HIP_TRY(hipMemcpy(d_stage, llr, copy_bytes, hipMemcpyHostToDevice));
+        d_in = d_stage;
+        if (sym) {
+            const double *d_llr = nullptr;
+            if ((rc = bicm_front(h, sym->cid, sym->n0, d_stage, llr_f32, B, nullptr, &d_llr))) return rc;
+            d_in = d_llr; llr_f32 = 0;
+        }
+    }
     int deferred = 0;
     if ((rc = decode_impl(h, d_in, llr_f32, B, nullptr, L, h->d_out.p, nullptr, nullptr, nullptr, nullptr, 1, &deferred))) return rc;
     if (deferred) {
@@ -295,7 +324,7 @@ static int host_decode(polar_code_t *h, const void *llr, int llr_f32, long B, in
 }
 
 int polar_decode_scl_llr_batch(polar_code_t *h, const double *llr, long B, int L, uint8_t *out) {
-    return host_decode(h, llr, 0, B, L, out);
+    return host_decode(h, llr, 0, nullptr, B, L, out);
 }
 
 int polar_decode_scl_llr(polar_code_t *h, const double *llr, int L, uint8_t *out) {
@@ -303,6 +332,6 @@ int polar_decode_scl_llr(polar_code_t *h, const double *llr, int L, uint8_t *out
 }
 
 int polar_decode_scl_llr_batch_f32(polar_code_t *h, const float *llr, long B, int L, uint8_t *out) {
-    return host_decode(h, llr, 1, B, L, out);
+    return host_decode(h, llr, 1, nullptr, B, L, out);
 }
 

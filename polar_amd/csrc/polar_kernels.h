@@ -133,6 +133,8 @@ struct PolarEncodeParams {
     double *llr;                 // [B][N]
     uint8_t *info_out;           // [B][K] or nullptr
     const unsigned int *n_dev;   // device: only the first min(B, *n_dev) rows exist (Monte-Carlo alive lists), nullptr = B
+    double *y_out;               // [B][N / n_bits] or nullptr: the received symbols of the ASK / BICM workload; with llr == nullptr
+                                 // the demapper is left out (polar_synth_bicm_sym_dev)
 };
 hipError_t polar_launch_encode(const PolarEncodeParams &p, hipStream_t st);
 hipError_t polar_launch_synth(const PolarEncodeParams &p, hipStream_t st);   // BPSK or ASK/BICM by p.constellation
@@ -146,6 +148,21 @@ hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0,
 hipError_t polar_launch_mc_count_compact(const uint8_t *decoded, const uint8_t *sent, long B, int K,
                                          const uint64_t *alive_in, const unsigned *n_in, uint64_t *alive_out, unsigned *n_out,
                                          unsigned long long *ctr, hipStream_t st);
+
+// BICM demapper on its own (polar_channel.hip; Constellation.m:123-144, include/polar_synth.h polar_synth_bicm_demap2): received
+// symbols y [B][M], M = N / nb (floor) -> llr / p1 [B][N], position i*nb + j = label bit j of symbol i; the tail positions
+// M*nb .. N-1 get llr = 0, p1 = 0.5 (as synth_kernel)
+struct PolarDemapParams {
+    int N, M, nb;
+    long B;
+    const void *y;               // [B][M] device, double or float
+    int y_f32;                   // 1: y are floats (widened exactly in the load)
+    double n0;
+    double pt[16];               // polar_const_point(id, s) / polar_const_norm(id), symbol index order
+    double *llr, *p1;            // [B][N] device; either may be nullptr
+    const unsigned int *n_dev;   // device: only the first min(B, *n_dev) rows exist, nullptr = B
+};
+hipError_t polar_launch_bicm_demap(const PolarDemapParams &p, hipStream_t st);
 
 // Multi-level coding receiver over set-partition (or Gray) ASK (polar_kernels_mlc.hip, include/polar_synth.h):
 // nb component codes of length M = N / nb = 2^m, component k = message positions k*M .. (k+1)*M - 1 (layer-major)

@@ -240,6 +240,23 @@ int polar_synth_bicm_llr_dev(polar_code_t *h, int constellation, uint64_t seed, 
     HIP_TRY(polar_launch_synth(p, (hipStream_t)stream));
     return POLAR_OK;
 }
+// the received symbols [B][N / n_bits] of the same trials (synth_kernel without its demapper): what a symbol-domain receiver is fed
+int polar_synth_bicm_sym_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double snr_db,
+                             double *d_y, uint8_t *d_info, void *stream) {
+    if (!h || !d_y) return fail(POLAR_E_ARG, "NULL argument");
+    if (constellation < POLAR_CONST_ASK4_GRAY || constellation > POLAR_CONST_ASK16_SP || constellation == POLAR_CONST_BPSK)
+        return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
+    if (B <= 0) return B == 0 ? POLAR_OK : fail(POLAR_E_ARG, "negative batch");
+    DevGuard dg_;
+    int rc = ensure_device(h, dg_);
+    if (rc) return rc;
+    PolarEncodeParams p;
+    fill_enc(h, p);
+    p.B = B; p.seed = seed; p.trial0 = trial0; p.y_out = d_y; p.info_out = d_info;
+    fill_channel(h, p, constellation, snr_db);
+    HIP_TRY(polar_launch_synth(p, (hipStream_t)stream));
+    return POLAR_OK;
+}
 
 // MLC construction (PolarCode.m:155-161, 180-190): per run nb x M random message bits, component encoding, genie-aided
 // multistage decoding; num_err layer-major
