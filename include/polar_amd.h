@@ -107,12 +107,27 @@ int polar_decode_scl_llr_batch_dev(polar_code_t *h, const double *d_llr, long B,
 int polar_decode_scl_llr_batch_f32(polar_code_t *h, const float *llr, long B, int L, uint8_t *out);
 int polar_decode_scl_llr_batch_dev_f32(polar_code_t *h, const float *d_llr, long B, int L, uint8_t *d_out,
                                        double *d_pm, void *stream);
+/* The same two calls for any element format of the channel LLRs. POLAR_LLR_F64 / _F32 are the entry points above (which forward
+ * here); POLAR_LLR_F16 (IEEE binary16) and POLAR_LLR_BF16 (bfloat16) take raw 16-bit patterns — what a half / bfloat16
+ * tensor or a numpy float16 array holds — at a quarter of the doubles' PCIe / HBM input bytes. The contract is the
+ * float form's, word for word: out == decode_scl_llr(widen(llr)), bit for bit, widen = the exact value of the pattern as a
+ * double (signed zeros, subnormals, +-inf and NaN patterns included: they behave as the same doubles behave). The widening
+ * happens in the loads of the kernels that read the caller's rows (integer operations on the pattern: no denormal mode can
+ * flush a subnormal); an aligned batch is never copied. Any other `fmt` is POLAR_E_ARG, before the device is touched; so are
+ * 16-bit rows at an odd address. */
+#define POLAR_LLR_F64  0
+#define POLAR_LLR_F32  1
+#define POLAR_LLR_F16  2
+#define POLAR_LLR_BF16 3
+int polar_decode_scl_llr_batch_fmt(polar_code_t *h, const void *llr, int fmt, long B, int L, uint8_t *out);
+int polar_decode_scl_llr_batch_dev_fmt(polar_code_t *h, const void *d_llr, int fmt, long B, int L, uint8_t *d_out,
+                                       double *d_pm, void *stream);
 /* Pre-size the handle's device scratch for decodes of up to B codewords at list sizes 1 .. L (runs one decode per kernel
  * family on generated inputs — the list-size-1 kernel, the 2-lane groups, every power-of-two lane group up to L, with and
  * without d_pm — and waits for them). The device-resident entry points grow their scratch on demand — a hipFree/hipMalloc,
  * i.e. an implicit device synchronisation, whenever B or L exceeds anything seen before; after polar_reserve they do not
- * allocate for calls of at most B codewords and list size at most L, double or float LLRs, under the handle's current mode and
- * tuning (tests/test_gpu_parity.py asserts it on the allocation counter, polar_debug_get "allocs").
+ * allocate for calls of at most B codewords and list size at most L, LLRs of any format (double, float, fp16, bf16), under the handle's current mode and
+ * tuning (tests/test_gpu_parity.py and tests/test_gpu_llr16.py assert it on the allocation counter, polar_debug_get "allocs").
  * d_llr needs the natural alignment of its element type; rows that start 16-byte aligned (any hipMalloc'ed batch) let the
  * list-size-1 kernel read them in place, other pointers are decoded through a converted copy (same results). */
 int polar_reserve(polar_code_t *h, long B, int L);

@@ -34,6 +34,18 @@ RX_MLC = 0x100                 # include/polar_amd.h POLAR_RX_MLC
 RECEIVERS = ("bicm", "mlc")
 
 
+LLR_F64, LLR_F32, LLR_F16, LLR_BF16 = 0, 1, 2, 3     # include/polar_amd.h POLAR_LLR_*
+LLR_FORMATS = {"f64": LLR_F64, "f32": LLR_F32, "f16": LLR_F16, "bf16": LLR_BF16}
+
+
+def _llr_fmt_code(fmt):
+    if isinstance(fmt, str):
+        if fmt not in LLR_FORMATS:
+            raise PolarError(f"unknown LLR format {fmt!r} (supported: {sorted(LLR_FORMATS)})")
+        return LLR_FORMATS[fmt]
+    return int(fmt)
+
+
 def _rx_flag(receiver):
     if receiver not in RECEIVERS:
         raise PolarError(f"unknown receiver {receiver!r} (supported: {RECEIVERS})")
@@ -403,31 +415,50 @@ class PolarCode:
         return out[0] if single else out
 
     # ---- decoders -----------------------------------------------------------------------
-    def decode_scl_llr(self, llr, list_size, out=None):
-        """PolarCode::decode_scl_llr (PolarCode.cpp:130-148). `llr` is [N] or [B, N]; float32 arrays
-        travel as float32 and are widened exactly on the device, anything else is taken as float64.
+    def decode_scl_llr(self, llr, list_size, out=None, fmt=None):
+        """PolarCode::decode_scl_llr (PolarCode.cpp:130-148). `llr` is [N] or [B, N]; float32 and float16 arrays travel as
+        they are and are widened exactly on the device, anything else is taken as float64. fmt="bf16": `llr` holds bfloat16
+        bit patterns as uint16 (numpy has no bfloat16); fmt="f16" takes binary16 patterns as uint16 likewise. The result is
+        the float64 call's on the widened values, bit for bit.
         out (optional): a C-contiguous uint8 [B, K] array to receive the bits (a caller that decodes batch after batch keeps
         one: a fresh 64-MiB array costs its page faults on every call)."""
-        f32 = isinstance(llr, np.ndarray) and llr.dtype == np.float32
-        a = np.ascontiguousarray(llr) if f32 else np.ascontiguousarray(llr, np.float64)
+        if fmt is not None:
+            code = _llr_fmt_code(fmt)
+            if code >= LLR_F16:
+                ok = (np.uint16, np.float16) if code == LLR_F16 else (np.uint16,)
+                if not (isinstance(llr, np.ndarray) and llr.dtype in ok):
+                    raise PolarError("fmt=%r takes the 16-bit patterns as a uint16 array%s" %
+                                     (fmt, " (or the values as float16)" if code == LLR_F16 else ""))
+                a = np.ascontiguousarray(llr)
+            else:
+                a = np.ascontiguousarray(llr, np.float32 if code == LLR_F32 else np.float64)
+        elif isinstance(llr, np.ndarray) and llr.dtype == np.float32:
+            code, a = LLR_F32, np.ascontiguousarray(llr)
+        elif isinstance(llr, np.ndarray) and llr.dtype == np.float16:
+            code, a = LLR_F16, np.ascontiguousarray(llr)
+        else:
+            code, a = LLR_F64, np.ascontiguousarray(llr, np.float64)
         single = a.ndim == 1
         a2 = a.reshape(-1, self.N)
         if out is None:
             out = np.zeros((a2.shape[0], self.K), np.uint8)
         elif out.dtype != np.uint8 or out.shape != (a2.shape[0], self.K) or not out.flags.c_contiguous:
             raise PolarError("out must be a C-contiguous uint8 array of shape [B, K]")
-        if f32:
-            self._chk(self._L.polar_decode_scl_llr_batch_f32(self._h, _p(a2, C.POINTER(C.c_float)), C.c_long(a2.shape[0]),
-                                                        C.c_int(list_size), _p(out, _u8p)))
-        else:
-            self._chk(self._L.polar_decode_scl_llr_batch(self._h, _p(a2, _dp), C.c_long(a2.shape[0]), C.c_int(list_size),
-                                                    _p(out, _u8p)))
+        self._chk(self._L.polar_decode_scl_llr_batch_fmt(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(a2.shape[0]),
+                                                    C.c_int(list_size), _p(out, _u8p)))
         return out[0] if single else out
 
     def decode_scl_llr_dev_f32(self, llr_ptr, B, list_size, out_ptr, pm_ptr=0, stream=None):
         """Device-resident float32 LLRs [B, N] -> uint8 [B, K]; asynchronous on `stream`."""
         self._chk(self._L.polar_decode_scl_llr_batch_dev_f32(self._h, C.c_void_p(llr_ptr), C.c_long(B), C.c_int(list_size),
                                                         C.c_void_p(out_ptr), C.c_void_p(pm_ptr), _stream_ptr(stream)))
+
+    def decode_scl_llr_dev_fmt(self, llr_ptr, fmt, B, list_size, out_ptr, pm_ptr=0, stream=None):
+        """Device-resident LLRs [B, N] of element format `fmt` ("f64", "f32", "f16", "bf16" or a POLAR_LLR_* code) -> uint8
+        [B, K]; asynchronous on `stream`. A torch.float16 / torch.bfloat16 tensor's data_ptr() is what "f16" / "bf16" take."""
+        self._chk(self._L.polar_decode_scl_llr_batch_dev_fmt(self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B),
+                                                        C.c_int(list_size), C.c_void_p(out_ptr), C.c_void_p(pm_ptr),
+                                                        _stream_ptr(stream)))
 
     def decode_scl_p1(self, p1, p0, list_size):
         """PolarCode::decode_scl_p1 (PolarCode.cpp:110-128)."""

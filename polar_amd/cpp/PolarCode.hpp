@@ -76,6 +76,16 @@ public:
         check(polar_decode_scl_llr_batch_f32(_h, llr.data(), B, list_size, out.data()));
         return out;
     }
+    // 16-bit LLRs as raw bit patterns: llr_format = POLAR_LLR_F16 (IEEE binary16) or POLAR_LLR_BF16 (bfloat16), each widened
+    // exactly on the device (a quarter of the doubles' bytes on the link)
+    std::vector<uint8_t> decode_scl_llr_batch(const std::vector<uint16_t> &llr, int llr_format, uint16_t list_size) {
+        need(llr_format == POLAR_LLR_F16 || llr_format == POLAR_LLR_BF16, "decode_scl_llr_batch: 16-bit patterns are POLAR_LLR_F16 or POLAR_LLR_BF16");
+        need(llr.size() % _block_length == 0, "decode_scl_llr_batch: size must be a multiple of block_length");
+        const long B = (long)(llr.size() / _block_length);
+        std::vector<uint8_t> out((size_t)B * _info_length);
+        check(polar_decode_scl_llr_batch_fmt(_h, llr.data(), llr_format, B, list_size, out.data()));
+        return out;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

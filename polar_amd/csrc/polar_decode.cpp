@@ -34,7 +34,7 @@ extern "C" {
 // ------------------------------------------------------------------------------------------
 int polar_decode_scl_llr_batch_dev(polar_code_t *h, const double *d_llr, long B, int L, uint8_t *d_out,
                                    double *d_pm, void *stream) {
-    return polar_decode_scl_llr_batch_dev_ev(h, d_llr, B, L, d_out, d_pm, stream, nullptr, nullptr);
+    return polar_decode_scl_llr_batch_dev_fmt(h, d_llr, POLAR_LLR_F64, B, L, d_out, d_pm, stream);
 }
 
 // list size 1, small batches: one codeword per wave, whole state in LDS (sc_lat_kernel)
@@ -55,7 +55,7 @@ int polar_decode_scl_llr_batch_dev_ev(polar_code_t *h, const double *d_llr, long
 // B rows are allocated; when n_dev != nullptr only the first min(B, *n_dev) exist (count read on the device)
 }  // extern "C"
 
-int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_f32, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
+int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
                             double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase, int *deferred) {
     if (!h || !d_llr || !d_out) return fail(POLAR_E_ARG, "NULL argument");
     if (deferred) *deferred = 0;
@@ -115,7 +115,7 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_f32, long 
         p.prefix_q = Q;
         p.prefix_len = Q ? std::min(P, Q) : 0;
     }
-    p.llr = (const double *)d_llr; p.llr_f32 = llr_f32; p.p0 = nullptr; p.out = d_out; p.pm_out = d_pm;
+    p.llr = (const double *)d_llr; p.llr_fmt = llr_fmt; p.p0 = nullptr; p.out = d_out; p.pm_out = d_pm;
     p.frozen = h->d_frozen.p; p.info_rank = h->d_info_rank.p; p.crc_mask = h->d_crc_mask.p; p.tabs = h->d_tabs.p;
     p.ctl = h->d_ctl.p;
     p.pre = nullptr;
@@ -160,10 +160,10 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_f32, long 
         p.llr_scr = h->d_llr_scr.p;
         if (phase != 2) {
             HIP_TRY(hipMemsetAsync(ctrl, 0, (4 + nfw) * sizeof(unsigned int), st));
-            if (!fold && !lat) HIP_TRY(polar_launch_sc8_front(d_llr, llr_f32, h->d_ech.p, fwords, h->d_tabs.p, h->n, B, n_dev, st));
+            if (!fold && !lat) HIP_TRY(polar_launch_sc8_front(d_llr, llr_fmt, h->d_ech.p, fwords, h->d_tabs.p, h->n, B, n_dev, st));
             PolarScParams sp;
             sp.n = h->n; sp.N = h->N; sp.K = h->K; sp.B = B;
-            sp.llr = (fold || lat) ? d_llr : nullptr; sp.llr_f32 = llr_f32;
+            sp.llr = (fold || lat) ? d_llr : nullptr; sp.llr_fmt = llr_fmt;
             sp.ech_t = (fold || lat) ? nullptr : h->d_ech.p; sp.out = d_out; sp.ops = h->d_sc_ops.p; sp.n_ops = (int)h->sc_ops.size();
             sp.order = h->d_order.p; sp.tabs = h->d_tabs.p; sp.a_scr = h->d_llr_scr.p;
             sp.flag_words = fwords; sp.work = ctrl; sp.n_dev = n_dev;
@@ -246,9 +246,9 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_f32, long 
     HIP_TRY(hipMemsetAsync(h->d_count.p, 0, sizeof(unsigned int), st));
     // (round 4: where the prefix kernel's first pass is staged through LDS it converts the raw rows itself — no conversion pass)
     const bool fuse_front = p.prefix_q > 0 && polar_prefix_is_staged(h->N) && !h->knobs.no_fuse_front;
-    if (!fuse_front) HIP_TRY(polar_launch_ed_front(d_llr, llr_f32, h->d_ech.p, h->d_flags.p, h->d_tabs.p, h->N, B, n_dev, st));
+    if (!fuse_front) HIP_TRY(polar_launch_ed_front(d_llr, llr_fmt, h->d_ech.p, h->d_flags.p, h->d_tabs.p, h->N, B, n_dev, st));
     PolarDecodeParams pe = p;
-    pe.llr = h->d_ech.p; pe.llr_f32 = 0; pe.flags = h->d_flags.p;
+    pe.llr = h->d_ech.p; pe.llr_fmt = POLAR_LLR_F64; pe.flags = h->d_flags.p;
     if (gs == 32 && !pipe && h->N >= 1024 && p.prefix_q > 0 && !h->knobs.no_tables) {
         // table mode: layers 1 and 2 as per-codeword value tables (polar_kernels.hip)
         if ((rc = h->d_tab_scr.ensure((size_t)grid * G * 3 * h->N + 64))) return rc;
@@ -257,7 +257,7 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_f32, long 
     }
     if (pe.prefix_q && fuse_front) {
         PolarDecodeParams pp = pe;
-        pp.llr = (const double *)d_llr; pp.llr_f32 = llr_f32;
+        pp.llr = (const double *)d_llr; pp.llr_fmt = llr_fmt;
         HIP_TRY(polar_launch_prefix(pp, true, h->d_ech.p, st));
     } else if (pe.prefix_q) HIP_TRY(polar_launch_prefix(pe, true, nullptr, st));
     if (ev_start) HIP_TRY(hipEventRecord((hipEvent_t)ev_start, st));
@@ -281,7 +281,14 @@ extern "C" {
 // touches the channel values (ed_front_kernel / prefix_kernel / the layer-1 visits) — no staging copy
 int polar_decode_scl_llr_batch_dev_f32(polar_code_t *h, const float *d_llr, long B, int L, uint8_t *d_out,
                                        double *d_pm, void *stream) {
-    return decode_impl(h, d_llr, 1, B, nullptr, L, d_out, d_pm, stream, nullptr, nullptr);
+    return polar_decode_scl_llr_batch_dev_fmt(h, d_llr, POLAR_LLR_F32, B, L, d_out, d_pm, stream);
+}
+// any element format (POLAR_LLR_*): 16-bit rows are bit patterns, widened exactly by integer operations in the same loads
+int polar_decode_scl_llr_batch_dev_fmt(polar_code_t *h, const void *d_llr, int fmt, long B, int L, uint8_t *d_out,
+                                       double *d_pm, void *stream) {
+    int rc = llr_fmt_check(fmt, d_llr);
+    if (rc) return rc;
+    return decode_impl(h, d_llr, fmt, B, nullptr, L, d_out, d_pm, stream, nullptr, nullptr);
 }
 
 // PolarCode::decode_scl_p1 (PolarCode.cpp:110-128): probability-domain SCL
@@ -314,7 +321,7 @@ int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p
     PolarDecodeParams p;
     p.n = h->n; p.N = N; p.K = h->K; p.crc = h->crc; p.L = L; p.W = h->W; p.B = B;
     p.prefix_q = 0; p.prefix_len = 0; p.ctl = nullptr; p.pre = nullptr; p.work = nullptr;
-    p.llr = h->d_in.p; p.llr_f32 = 0; p.p0 = h->d_in.p + (size_t)B * N; p.out = h->d_out.p; p.pm_out = nullptr;
+    p.llr = h->d_in.p; p.llr_fmt = POLAR_LLR_F64; p.p0 = h->d_in.p + (size_t)B * N; p.out = h->d_out.p; p.pm_out = nullptr;
     p.frozen = h->d_frozen.p; p.info_rank = h->d_info_rank.p; p.crc_mask = h->d_crc_mask.p; p.tabs = h->d_tabs.p;
     p.llr_scr = h->d_llr_scr.p; p.c_scr = h->d_c_scr.p; p.hist_scr = h->d_hist_scr.p;
     p.flags = nullptr; p.cw_list = nullptr; p.cw_count = nullptr; p.n_dev = nullptr; p.tab_scr = nullptr; p.var_scr = nullptr;

@@ -26,6 +26,36 @@ struct P16 {
     }
 };
 
+// 16-bit channel LLRs (polar_kernels.h POLAR_LLR_F16 / _BF16) arrive as raw bit patterns and are widened to the double of
+// the SAME value with integer operations on the pattern: EB exponent bits, MB mantissa bits (binary16: 5, 10; bfloat16: 8, 7).
+// No float conversion instruction is involved, so no denormal mode can flush anything: a subnormal pattern m 2^(1 - BIAS - MB)
+// is built as the double 2^(1 - BIAS) (1 + m 2^-MB) minus 2^(1 - BIAS) — both multiples of the result's unit, the difference
+// exact. Signed zeros, infinities and NaN payloads (shifted into the top mantissa bits) come out as a widening conversion
+// gives them.
+template <int EB, int MB>
+__device__ __forceinline__ double widen16(unsigned u) {
+    constexpr unsigned EMAX = (1u << EB) - 1u;
+    constexpr int BIAS = (1 << (EB - 1)) - 1;
+    const unsigned e = (u >> MB) & EMAX, m = u & ((1u << MB) - 1u);
+    const unsigned de = (e == EMAX) ? 0x7FFu : (e ? e : 1u) + (unsigned)(1023 - BIAS);
+    double d = __hiloint2double((int)((de << 20) | (m << (20 - MB))), 0);
+    const double unit = __hiloint2double((int)((unsigned)(1023 + 1 - BIAS) << 20), 0);      // 2^(1 - BIAS)
+    d = e ? d : d - unit;
+    return __hiloint2double(__double2hiint(d) | (int)((u & 0x8000u) << 16), __double2loint(d));
+}
+struct polar_f16 { uint16_t u; };
+struct polar_bf16 { uint16_t u; };
+__device__ __forceinline__ double llr_widen(double x) { return x; }
+__device__ __forceinline__ double llr_widen(float x) { return (double)x; }
+__device__ __forceinline__ double llr_widen(polar_f16 x) { return widen16<5, 10>(x.u); }
+__device__ __forceinline__ double llr_widen(polar_bf16 x) { return widen16<8, 7>(x.u); }
+// element i of caller rows in one of the narrow formats (fmt != 0: POLAR_LLR_F32, _F16, _BF16), widened
+__device__ __forceinline__ double llr_load_narrow(const void *rows, size_t i, int fmt) {
+    if (fmt == 1) return (double)reinterpret_cast<const float *>(rows)[i];
+    const unsigned u = reinterpret_cast<const uint16_t *>(rows)[i];
+    return fmt == 2 ? widen16<5, 10>(u) : widen16<8, 7>(u);
+}
+
 __device__ __forceinline__ double shfl_d(double v, int src) { return __shfl(v, src, 64); }
 __device__ __forceinline__ double readlane_d(double v, int src) {      // src wave-uniform: result lives in SGPRs
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);

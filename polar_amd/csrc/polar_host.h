@@ -340,9 +340,12 @@ int upload(DevBuf<T> &d, const std::vector<T> &v) {
 // phase (list size 1 with the one-codeword-per-wave kernel only): 0 = everything; 1 = the decode kernel alone — the caller
 // looks at the flag words itself and runs phase 2 (work list + general kernel over the flagged codewords) only when one is
 // set; *deferred reports whether phase 1 really left the fallback out
-int decode_impl(polar_code *h, const void *d_llr, int llr_f32, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
+int decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
                 double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase = 0, int *deferred = nullptr);
 bool use_sc_lat(const polar_code *h, long B);
+// (polar_kernels.h repeats the POLAR_LLR_* codes of include/polar_amd.h for the translation units that do not see the public header)
+static_assert(POLAR_LLR_F64 == 0 && POLAR_LLR_F32 == 1 && POLAR_LLR_F16 == 2 && POLAR_LLR_BF16 == 3, "POLAR_LLR_* codes");
+int llr_fmt_check(int fmt, const void *rows);      // POLAR_E_ARG for an unknown POLAR_LLR_* code or 16-bit rows at an odd address (polar_hostpipe.cpp)
 void fill_enc(const polar_code *h, PolarEncodeParams &p);
 // MLC receiver (polar_kernels_mlc.hip): *cid = the constellation without POLAR_RX_MLC, after the checks of include/polar_amd.h
 int mlc_check(const polar_code *h, int constellation, int *cid);
@@ -357,7 +360,7 @@ int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, lo
 // polar_hostpipe.cpp
 // rows that are received symbols instead of LLRs (polar_decode_bicm_batch*): M elements per row, demapped on the device
 struct SymRows { int cid, M; double n0; };
-int host_decode(polar_code *h, const void *rows, int rows_f32, const SymRows *sym, long B, int L, uint8_t *out);
+int host_decode(polar_code *h, const void *rows, int rows_fmt, const SymRows *sym, long B, int L, uint8_t *out);
 void hostpipe_release(polar_code *h);
 // polar_multi.cpp
 void multi_release(polar_code *h, bool abort_comms);

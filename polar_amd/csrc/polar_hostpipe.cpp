@@ -109,11 +109,11 @@ static int hostpipe_ensure(polar_code_t *h, size_t in_slot, size_t out_slot, int
 
 // *no_staging is set when the call failed BEFORE anything was decoded because the staging slots / decode lanes could not be set
 // up (host_decode then takes the unpipelined path)
-static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, const SymRows *sym, long B, int L, uint8_t *out, long chunk_cw, int lanes, int threads, bool ramp, bool *no_staging) {
+static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_fmt, const SymRows *sym, long B, int L, uint8_t *out, long chunk_cw, int lanes, int threads, bool ramp, bool *no_staging) {
     using clk = std::chrono::steady_clock;
     auto us = [](clk::time_point a, clk::time_point b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
     const clk::time_point t_begin = clk::now();
-    const size_t esz = llr_f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = polar_llr_esz(llr_fmt);          // (symbol rows: doubles or floats only)
     const size_t row_in = (size_t)(sym ? sym->M : h->N) * esz, row_out = (size_t)h->K;          // (symbol rows: M elements, demapped on the lane)
     // The chunks. A launch of the list kernels takes milliseconds whatever it carries (the N-step chain of one wave), so
     // (a) the first chunks are SMALL — an eighth of the full size, doubling: the device starts a fraction of a millisecond
@@ -169,13 +169,13 @@ static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, 
         if (e != hipSuccess) { rc = fail(POLAR_E_DEVICE, "host pipeline: copy of chunk %ld: %s", k, hipGetErrorString(e)); break; }
         polar_code *c = l ? hp->ctx[l] : h;
         const void *d_rows = hp->d_in[slot];
-        int rows_f32 = llr_f32;
+        int rows_fmt = llr_fmt;
         if (sym) {          // the demap launch precedes the decode on the lane's stream; each lane's context owns its LLR rows
             const double *d_llr = nullptr;
-            if ((rc = bicm_front(c, sym->cid, sym->n0, d_rows, llr_f32, nb, st, &d_llr))) break;
-            d_rows = d_llr; rows_f32 = 0;
+            if ((rc = bicm_front(c, sym->cid, sym->n0, d_rows, llr_fmt, nb, st, &d_llr))) break;
+            d_rows = d_llr; rows_fmt = POLAR_LLR_F64;
         }
-        if ((rc = decode_impl(c, d_rows, rows_f32, nb, nullptr, L, hp->d_out[slot], nullptr, st, nullptr, nullptr))) break;
+        if ((rc = decode_impl(c, d_rows, rows_fmt, nb, nullptr, L, hp->d_out[slot], nullptr, st, nullptr, nullptr))) break;
         e = hipMemcpyAsync(hp->pin_out[slot], hp->d_out[slot], (size_t)nb * row_out, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipEventRecord(hp->done[slot], st);
         if (e != hipSuccess) { rc = fail(POLAR_E_DEVICE, "host pipeline: result copy of chunk %ld: %s", k, hipGetErrorString(e)); break; }
@@ -187,7 +187,7 @@ static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_f32, 
     return POLAR_OK;
 }
 
-int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const SymRows *sym, long B, int L, uint8_t *out) {
+int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const SymRows *sym, long B, int L, uint8_t *out) {
     if (!h || !llr || !out) return fail(POLAR_E_ARG, "NULL argument");
     if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
     if (B < 0) return fail(POLAR_E_ARG, "negative batch");
@@ -198,9 +198,11 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const
     // Symbol rows: the thresholds and chunk sizes below were fitted to LLR bytes, so they are applied to the LLR bytes the symbols
     // stand for (B * N doubles): a batch takes the form — zero-copy, one copy, pipelined, and the same chunks — that the LLR path
     // takes for this B. They were not re-measured for the narrower rows.
-    const size_t esz = sym ? sizeof(double) : (llr_f32 ? sizeof(float) : sizeof(double));
+    // LLR rows: the thresholds are applied to the bytes that travel, whatever the element (2, 4 or 8 bytes). They were fitted to
+    // doubles and floats and not refitted for the 16-bit formats.
+    const size_t esz = sym ? sizeof(double) : polar_llr_esz(llr_fmt);
     const size_t in_bytes = (size_t)B * h->N * esz, out_bytes = (size_t)B * h->K;
-    const size_t copy_bytes = sym ? (size_t)B * sym->M * (llr_f32 ? sizeof(float) : sizeof(double)) : in_bytes;          // what travels
+    const size_t copy_bytes = sym ? (size_t)B * sym->M * polar_llr_esz(llr_fmt) : in_bytes;          // what travels
     const int mode = h->knobs.mode_override >= 0 ? h->knobs.mode_override : h->mode;
     if (h->hpipe) h->hpipe->last_chunks = 0;
     {
@@ -238,7 +240,7 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const
             const int threads = kn.host_threads > 0 ? (int)std::min<long>(kn.host_threads, 64) : std::max(1, std::min(8, usable_cpus() / 2));
             if (B > chunk_cw) {
                 bool no_staging = false;
-                rc = host_decode_pipelined(h, llr, llr_f32, sym, B, L, out, chunk_cw, lanes, threads, ramp, &no_staging);
+                rc = host_decode_pipelined(h, llr, llr_fmt, sym, B, L, out, chunk_cw, lanes, threads, ramp, &no_staging);
                 // (no staging memory: the batch is decoded by the unpipelined path below, as round 4 decoded every batch)
                 if (!no_staging) return rc;
                 if (h->hpipe) h->hpipe->last_chunks = -1;          // (polar_debug_get "host_chunks" = -1: the fallback was taken)
@@ -264,22 +266,22 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const
         }
         memcpy(h->pin_in, llr, copy_bytes);
         const void *d_rows = h->pin_in_dev;
-        int rows_f32 = llr_f32;
+        int rows_fmt = llr_fmt;
         if (sym) {          // demap first (the kernel reads the mapped symbols), then the latency kernel on the LLR rows in HBM
             const double *d_llr = nullptr;
-            if ((rc = bicm_front(h, sym->cid, sym->n0, d_rows, llr_f32, B, nullptr, &d_llr))) return rc;
-            d_rows = d_llr; rows_f32 = 0;
+            if ((rc = bicm_front(h, sym->cid, sym->n0, d_rows, llr_fmt, B, nullptr, &d_llr))) return rc;
+            d_rows = d_llr; rows_fmt = POLAR_LLR_F64;
         }
         int deferred = 0;
         h->lat_flag_bytes = h->pin_out_dev + out_bytes;
-        rc = decode_impl(h, d_rows, rows_f32, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 1, &deferred);
+        rc = decode_impl(h, d_rows, rows_fmt, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 1, &deferred);
         h->lat_flag_bytes = nullptr;
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));
         bool any = !deferred;
         for (long i = 0; i < B && !any; ++i) any = h->pin_out[out_bytes + i] != 0;
         if (any && deferred) {
-            if ((rc = decode_impl(h, d_rows, rows_f32, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
+            if ((rc = decode_impl(h, d_rows, rows_fmt, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
             HIP_TRY(hipStreamSynchronize(nullptr));
         }
         memcpy(out, h->pin_out, out_bytes);
@@ -289,19 +291,20 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const
     {
         const size_t n_in = (size_t)B * (sym ? sym->M : h->N);
         void *d_stage;
-        if (llr_f32) { if ((rc = h->d_f32.ensure(n_in))) return rc; d_stage = h->d_f32.p; }
+        // (the narrow formats share one staging buffer, counted in floats: two 16-bit elements each)
+        if (llr_fmt) { if ((rc = h->d_f32.ensure(llr_fmt == POLAR_LLR_F32 ? n_in : (n_in + 1) / 2))) return rc; d_stage = h->d_f32.p; }
         else { if ((rc = h->d_in.ensure(n_in))) return rc; d_stage = h->d_in.p; }
         if ((rc = h->d_out.ensure(out_bytes))) return rc;
         HIP_TRY(hipMemcpy(d_stage, llr, copy_bytes, hipMemcpyHostToDevice));
         d_in = d_stage;
         if (sym) {
             const double *d_llr = nullptr;
-            if ((rc = bicm_front(h, sym->cid, sym->n0, d_stage, llr_f32, B, nullptr, &d_llr))) return rc;
-            d_in = d_llr; llr_f32 = 0;
+            if ((rc = bicm_front(h, sym->cid, sym->n0, d_stage, llr_fmt, B, nullptr, &d_llr))) return rc;
+            d_in = d_llr; llr_fmt = POLAR_LLR_F64;
         }
     }
     int deferred = 0;
-    if ((rc = decode_impl(h, d_in, llr_f32, B, nullptr, L, h->d_out.p, nullptr, nullptr, nullptr, nullptr, 1, &deferred))) return rc;
+    if ((rc = decode_impl(h, d_in, llr_fmt, B, nullptr, L, h->d_out.p, nullptr, nullptr, nullptr, nullptr, 1, &deferred))) return rc;
     if (deferred) {
         HIP_TRY(hipMemcpy(out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost));          // (waits for the kernel)
         bool any = false;
@@ -316,15 +319,29 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_f32, const
             for (uint8_t b : fb) any |= (b != 0);
         }
         if (!any) return POLAR_OK;
-        if ((rc = decode_impl(h, d_in, llr_f32, B, nullptr, L, h->d_out.p, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
+        if ((rc = decode_impl(h, d_in, llr_fmt, B, nullptr, L, h->d_out.p, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost));
     return POLAR_OK;
 }
 
+// the element formats of the channel LLRs (include/polar_amd.h POLAR_LLR_*): checked before anything touches the device
+int polar_host::llr_fmt_check(int fmt, const void *rows) {
+    if (fmt < POLAR_LLR_F64 || fmt > POLAR_LLR_BF16)
+        return fail(POLAR_E_ARG, "unknown LLR format %d (POLAR_LLR_F64 = 0, _F32 = 1, _F16 = 2, _BF16 = 3)", fmt);
+    if (fmt >= POLAR_LLR_F16 && ((uintptr_t)rows & 1u)) return fail(POLAR_E_ARG, "16-bit LLR rows at an odd address");
+    return POLAR_OK;
+}
+
+int polar_decode_scl_llr_batch_fmt(polar_code_t *h, const void *llr, int fmt, long B, int L, uint8_t *out) {
+    int rc = llr_fmt_check(fmt, llr);
+    if (rc) return rc;
+    return host_decode(h, llr, fmt, nullptr, B, L, out);
+}
+
 int polar_decode_scl_llr_batch(polar_code_t *h, const double *llr, long B, int L, uint8_t *out) {
-    return host_decode(h, llr, 0, nullptr, B, L, out);
+    return polar_decode_scl_llr_batch_fmt(h, llr, POLAR_LLR_F64, B, L, out);
 }
 
 int polar_decode_scl_llr(polar_code_t *h, const double *llr, int L, uint8_t *out) {
@@ -332,6 +349,5 @@ int polar_decode_scl_llr(polar_code_t *h, const double *llr, int L, uint8_t *out
 }
 
 int polar_decode_scl_llr_batch_f32(polar_code_t *h, const float *llr, long B, int L, uint8_t *out) {
-    return host_decode(h, llr, 1, nullptr, B, L, out);
+    return polar_decode_scl_llr_batch_fmt(h, llr, POLAR_LLR_F32, B, L, out);
 }
-

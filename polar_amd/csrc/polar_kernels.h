@@ -4,13 +4,22 @@
 #include <stdint.h>
 #include <stddef.h>
 
+// element formats of the caller's channel LLR rows (the values of include/polar_amd.h)
+#ifndef POLAR_LLR_F64
+#define POLAR_LLR_F64  0
+#define POLAR_LLR_F32  1
+#define POLAR_LLR_F16  2
+#define POLAR_LLR_BF16 3
+#endif
+static inline size_t polar_llr_esz(int fmt) { return fmt == POLAR_LLR_F64 ? 8 : fmt == POLAR_LLR_F32 ? 4 : 2; }
+
 struct PolarDecodeParams {
     int n, N, K, crc, L;
     int W;                       // 32-bit words of decision history = ceil((K+crc)/32)
     int prefix_q, prefix_len;    // all-frozen prefix handled cooperatively: block size Q (0 = off), leaves Pe
     long B;                      // codewords
-    const double *llr;           // [B][N] device (LLR mode: llr; probability mode: p1); floats when llr_f32
-    int llr_f32;                 // channel LLRs are float[B][N] (widened in the load)
+    const double *llr;           // [B][N] device (LLR mode: llr; probability mode: p1); elements of llr_fmt
+    int llr_fmt;                 // element format of the channel LLRs (POLAR_LLR_*; the narrow ones are widened exactly in the load)
     const double *p0;            // [B][N] device (probability mode only)
     uint8_t *out;                // [B][K] device
     double *pm_out;              // [B] device or nullptr
@@ -45,7 +54,7 @@ hipError_t polar_launch_decode_llr_ed1(const PolarDecodeParams &p, int gs, int l
 hipError_t polar_launch_decode_lat(const PolarDecodeParams &p, int gs, bool ed, int blocks, hipStream_t st);
 size_t polar_decode_lat_lds_bytes(int N, int gs, int W);
 hipError_t polar_launch_decode_llr(const PolarDecodeParams &p, int gs, int lds_log, int pipe, int grid, bool ed, hipStream_t st);
-hipError_t polar_launch_ed_front(const void *llr, int llr_f32, double *ech, uint8_t *flags, const double *tabs, int N, long B, const unsigned *n_dev, hipStream_t st);
+hipError_t polar_launch_ed_front(const void *llr, int llr_fmt, double *ech, uint8_t *flags, const double *tabs, int N, long B, const unsigned *n_dev, hipStream_t st);
 hipError_t polar_launch_ed_collect(const uint8_t *flags, long B, const unsigned *n_dev, uint32_t *list, unsigned *count, hipStream_t st);
 
 hipError_t polar_launch_decode_p1(const PolarDecodeParams &p, int gs, int grid, hipStream_t st);
@@ -69,8 +78,8 @@ struct PolarScParams {
     int n, N, K;
     long B;
     const double *ech_t;         // [B][N] device: channel values, stored form, kernel element order (sc8_front_kernel); unused when `llr` is set
-    const void *llr;             // nullptr, or [B][N] device: the caller's rows (double, or float when llr_f32), read IN PLACE by the two
-    int llr_f32;                 //   visits of the top layer (no front pass): polar_sc8_can_fold() says for which schedules
+    const void *llr;             // nullptr, or [B][N] device: the caller's rows (elements of llr_fmt: POLAR_LLR_*), read IN PLACE by the two
+    int llr_fmt;                 //   visits of the top layer (no front pass): polar_sc8_can_fold() says for which schedules
     uint8_t *out;                // [B][K] device
     const uint32_t *ops;         // [n_ops] device: schedule words = type | log2(S) << 3 | first leaf << 8
     int n_ops;                   //   type 0 F, 1 G, 3 all-unfrozen, 4 combine, 6 all-frozen bound
@@ -90,7 +99,7 @@ int polar_sc8_waves_per_cu(int N);
 size_t polar_sc8_scratch_doubles_per_wave(int N);
 int polar_sc8_fold_min_log();            // smallest log2(block length) whose top-layer visits can read the caller's rows in place
 int polar_sc8_min_global_log();          // log2 of the smallest HBM-resident layer of the list-size-1 kernel
-hipError_t polar_launch_sc8_front(const void *llr, int llr_f32, double *ech_p, unsigned int *flag_words, const double *tabs,
+hipError_t polar_launch_sc8_front(const void *llr, int llr_fmt, double *ech_p, unsigned int *flag_words, const double *tabs,
                                   int n, long B, const unsigned *n_dev, hipStream_t st);
 hipError_t polar_launch_sc8_decode(const PolarScParams &p, int grid_waves, hipStream_t st);
 // one codeword per wave, whole state in LDS: the latency form for small batches (N <= 2^polar_sc_lat_max_log())

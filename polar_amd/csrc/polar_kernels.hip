@@ -45,16 +45,27 @@
 
 #include "polar_llr_nodes.h"
 
-// Channel LLRs at the boundary are doubles (the reference's type) or floats (polar_decode_scl_llr_batch_dev_f32):
-// a float is widened — exactly — in the load itself, there is no staging copy. ch_row() = row `cw` of p.llr.
-template <bool ED>
+// Channel LLRs at the boundary are doubles (the reference's type), floats, or 16-bit floats as bit patterns (binary16 / bfloat16:
+// polar_decode_scl_llr_batch_dev_fmt): a narrow element is widened — exactly — in the load itself, there is no staging copy.
+// ch_row() = row `cw` of p.llr. NARROW16 = false: the instantiation never sees 16-bit rows (the exp-domain list kernels: their
+// p.llr is ed_front_kernel's / prefix_kernel's output) and keeps the double / float form it was tuned with.
+template <bool NARROW16>
 __device__ __forceinline__ const double *ch_row(const PolarDecodeParams &p, size_t cw, int N) {
-    return p.llr_f32 ? reinterpret_cast<const double *>(reinterpret_cast<const float *>(p.llr) + cw * (size_t)N)
+    if constexpr (NARROW16) {
+        if (p.llr_fmt >= POLAR_LLR_F16) return reinterpret_cast<const double *>(reinterpret_cast<const uint16_t *>(p.llr) + cw * (size_t)N);
+    }
+    return p.llr_fmt ? reinterpret_cast<const double *>(reinterpret_cast<const float *>(p.llr) + cw * (size_t)N)
                      : p.llr + cw * (size_t)N;
 }
-// (the exp-domain kernels never see floats — ed_front_kernel has widened and converted the channel values — but folding
-// that into the macro measured 1 % SLOWER on the headline kernel: register allocation of the hot loops shifts)
-#define CH(row, i) (p.llr_f32 ? (double)reinterpret_cast<const float *>(row)[i] : (row)[i])
+template <bool NARROW16>
+__device__ __forceinline__ double ch_narrow(const double *row, size_t i, int fmt) {
+    if constexpr (NARROW16) return llr_load_narrow(row, i, fmt);
+    else return (double)reinterpret_cast<const float *>(row)[i];
+}
+// (the exp-domain list kernels never see narrow rows at all, but folding that into the macro measured 1 % SLOWER on the headline
+// kernel: register allocation of the hot loops shifts. The test on the format is where the float test was; the 16-bit forms
+// branch inside its narrow arm. CH_N16 is a constant of the kernel that uses the macro.)
+#define CH(row, i) (p.llr_fmt ? ch_narrow<CH_N16>(row, i, p.llr_fmt) : (row)[i])
 
 // Layer storage helpers --------------------------------------------------------------------
 // LDS:    layers with S <= SL; layer of size S starts at element (S-1); element e at [e*64 + lane]
@@ -94,6 +105,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
     // PIPE=1: one wave per block (8 waves/CU, register double-buffering); PIPE=0: four independent
     // waves per block sharing the transcendental tables (16 waves/CU with LDS_LOG = 3)
     constexpr int WPB = PIPE ? 1 : 4;
+    constexpr bool CH_N16 = !ED;                   // 16-bit caller rows reach the LLR-domain instantiations only (see CH)
     constexpr int G = LAT ? 1 : 64 / GS;           // codewords per wave
     constexpr int EL = 64 / GS;                    // (LAT) lanes that share the elements of a path's layers
     // partial-sum and history words: one column per LANE ([word][64]); LAT: per PATH ([word][GS] — the 64 / GS lanes of a path hold
@@ -204,7 +216,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int i = i0 + 64 * k + lane;
-                    x[k] = (i < N) ? (p.llr_f32 ? (double)reinterpret_cast<const float *>(p.llr)[row + i] : p.llr[row + i]) : 1.0;
+                    x[k] = (i < N) ? (p.llr_fmt ? llr_load_narrow(p.llr, row + i, p.llr_fmt) : p.llr[row + i]) : 1.0;
                 }
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -419,6 +431,7 @@ __global__ __launch_bounds__(256) void prefix_kernel(PolarDecodeParams p, int st
     auto GN0 = [&](double a, double b) -> double {
         if constexpr (ED) return g_node_e(a, b, 0u, tb); else return g_node(a, b, 0u);
     };
+    constexpr bool CH_N16 = true;        // (the first pass reads the caller's rows in every format, exp-domain or not)
     const int lane = threadIdx.x & 63, lig = lane & 31, gbase = lane & 32;
     const int n = p.n, N = p.N, Q = p.prefix_q, Pe = p.prefix_len;
     const int R = Q >> 5;
@@ -427,7 +440,7 @@ __global__ __launch_bounds__(256) void prefix_kernel(PolarDecodeParams p, int st
     for (long c0 = (long)blockIdx.x * per_block; c0 < Bv; c0 += (long)gridDim.x * per_block) {
         const long cw = c0 + (threadIdx.x >> 5);
         const bool valid = cw < Bv;
-        const double *in0 = ch_row<ED>(p, (size_t)(valid ? cw : 0), N);
+        const double *in0 = ch_row<CH_N16>(p, (size_t)(valid ? cw : 0), N);
         double *pre = const_cast<double *>(p.pre) + (size_t)(valid ? cw : 0) * (size_t)(N - Q + 1);
         double x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         bool bad_in = false;                 // (fused conversion: this codeword's input guard)
@@ -652,7 +665,7 @@ __global__ __launch_bounds__(256) void ed_front_kernel(const TIN *llr, double *e
         bool any = false, sized = false;
         for (int i = lane; i < N; i += 64) {
             bool f;
-            const double x = (double)src[i];
+            const double x = llr_widen(src[i]);
             dst[i] = ed_from_channel(x, tb, f);
             any |= f;
             sized |= fabs(x) >= 0.1;
@@ -665,10 +678,12 @@ __global__ __launch_bounds__(256) void ed_front_kernel(const TIN *llr, double *e
         if (lane == 0) flags[cw] = bad ? 1 : 0;
     }
 }
-hipError_t polar_launch_ed_front(const void *llr, int llr_f32, double *ech, uint8_t *flags, const double *tabs, int N, long B, const unsigned *n_dev, hipStream_t st) {
+hipError_t polar_launch_ed_front(const void *llr, int llr_fmt, double *ech, uint8_t *flags, const double *tabs, int N, long B, const unsigned *n_dev, hipStream_t st) {
     long blocks = (B + 3) / 4;
     if (blocks > 16384) blocks = 16384;
-    if (llr_f32) hipLaunchKernelGGL(ed_front_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)llr, ech, flags, tabs, N, B, n_dev);
+    if (llr_fmt == POLAR_LLR_F32) hipLaunchKernelGGL(ed_front_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)llr, ech, flags, tabs, N, B, n_dev);
+    else if (llr_fmt == POLAR_LLR_F16) hipLaunchKernelGGL(ed_front_kernel<polar_f16>, dim3((unsigned)blocks), dim3(256), 0, st, (const polar_f16 *)llr, ech, flags, tabs, N, B, n_dev);
+    else if (llr_fmt == POLAR_LLR_BF16) hipLaunchKernelGGL(ed_front_kernel<polar_bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const polar_bf16 *)llr, ech, flags, tabs, N, B, n_dev);
     else hipLaunchKernelGGL(ed_front_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, (const double *)llr, ech, flags, tabs, N, B, n_dev);
     return hipGetLastError();
 }

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void sc8_front_kernel(const TIN *llr, double *
         // element e of the kernel's order is channel position bitrev_n(e)
         for (int i = threadIdx.x; i < N; i += 256) {
             bool f;
-            const double v = ed_from_channel((double)llr[(size_t)cw * N + i], tb, f);
+            const double v = ed_from_channel(llr_widen(llr[(size_t)cw * N + i]), tb, f);
             any |= f;
             if (staged) row[i] = v;
             else ech_p[(size_t)cw * N + (__brev((unsigned)i) >> (32 - n))] = v;
@@ -105,6 +105,9 @@ __global__ __launch_bounds__(256) void sc8_front_kernel(const TIN *llr, double *
     }
 }
 
+// W16: the instantiation for rows of 16-bit elements read in place (binary16 / bfloat16 bit patterns) — the double / float
+// instantiation is the kernel as it was, without a third arm in its top-layer load
+template <bool W16>
 __global__ __launch_bounds__(64 * SC8_WPB) void sc8_decode_kernel(PolarScParams p) {
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -206,7 +209,19 @@ __global__ __launch_bounds__(64 * SC8_WPB) void sc8_decode_kernel(PolarScParams 
                                 const size_t pos = (size_t)(valid ? cw : 0) * N + (size_t)(__brev((unsigned)sub) >> 29) * (size_t)(N / 8)
                                                    + (size_t)(__brev((unsigned)r) >> (32 - (p.n - 6))) * 8;
                                 double v[8];
-                                if (p.llr_f32) {
+                                if constexpr (W16) {
+                                    // eight 16-bit elements = ONE 16-byte load (half a 32-byte sector per lane, a quarter of the
+                                    // doubles' bytes), widened by integer operations on the patterns (widen16)
+                                    const uint4 x = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p.llr) + pos);
+                                    const unsigned w[4] = {x.x, x.y, x.z, x.w};
+                                    if (p.llr_fmt == POLAR_LLR_F16) {
+#pragma unroll
+                                        for (int i = 0; i < 4; ++i) { v[2 * i] = widen16<5, 10>(w[i] & 0xFFFFu); v[2 * i + 1] = widen16<5, 10>(w[i] >> 16); }
+                                    } else {
+#pragma unroll
+                                        for (int i = 0; i < 4; ++i) { v[2 * i] = widen16<8, 7>(w[i] & 0xFFFFu); v[2 * i + 1] = widen16<8, 7>(w[i] >> 16); }
+                                    }
+                                } else if (p.llr_fmt) {
                                     const float4 *q = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p.llr) + pos);
                                     const float4 x0 = q[0], x1 = q[1];
                                     v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
@@ -430,17 +445,21 @@ int polar_sc8_fold_min_log() { int l = 7; while ((1 << l) / 8 < 2 * SC8_SL) ++l;
 int polar_sc8_min_global_log() { int l = 0; while ((1 << l) < 2 * SC8_SL) ++l; return l; }
 int polar_sc8_waves_per_cu(int N) { const int w = (int)((160 * 1024) / polar_sc8_lds_bytes(N)) * SC8_WPB; return w > 32 ? 32 : w; }
 size_t polar_sc8_scratch_doubles_per_wave(int N) { return sc8_scratch_doubles(N); }
-hipError_t polar_launch_sc8_front(const void *llr, int llr_f32, double *ech_p, unsigned int *flag_words, const double *tabs,
+hipError_t polar_launch_sc8_front(const void *llr, int llr_fmt, double *ech_p, unsigned int *flag_words, const double *tabs,
                                   int n, long B, const unsigned *n_dev, hipStream_t st) {
     const unsigned blocks = (unsigned)(B < 65536 ? (B ? B : 1) : 65536);
     const int staged = (n <= 12) ? 1 : 0;                      // the row (<= 32 KiB) is permuted through LDS
     const size_t sh = staged ? ((size_t)8 << n) : 0;
-    if (llr_f32) hipLaunchKernelGGL(sc8_front_kernel<float>, dim3(blocks), dim3(256), sh, st, (const float *)llr, ech_p, flag_words, tabs, n, B, n_dev, staged);
+    if (llr_fmt == POLAR_LLR_F32) hipLaunchKernelGGL(sc8_front_kernel<float>, dim3(blocks), dim3(256), sh, st, (const float *)llr, ech_p, flag_words, tabs, n, B, n_dev, staged);
+    else if (llr_fmt == POLAR_LLR_F16) hipLaunchKernelGGL(sc8_front_kernel<polar_f16>, dim3(blocks), dim3(256), sh, st, (const polar_f16 *)llr, ech_p, flag_words, tabs, n, B, n_dev, staged);
+    else if (llr_fmt == POLAR_LLR_BF16) hipLaunchKernelGGL(sc8_front_kernel<polar_bf16>, dim3(blocks), dim3(256), sh, st, (const polar_bf16 *)llr, ech_p, flag_words, tabs, n, B, n_dev, staged);
     else hipLaunchKernelGGL(sc8_front_kernel<double>, dim3(blocks), dim3(256), sh, st, (const double *)llr, ech_p, flag_words, tabs, n, B, n_dev, staged);
     return hipGetLastError();
 }
 hipError_t polar_launch_sc8_decode(const PolarScParams &p, int grid_waves, hipStream_t st) {
-    hipLaunchKernelGGL(sc8_decode_kernel, dim3((grid_waves + SC8_WPB - 1) / SC8_WPB), dim3(64 * SC8_WPB), polar_sc8_lds_bytes(p.N), st, p);
+    // (16-bit rows read in place have an instantiation of their own; a front pass has already widened anything else)
+    if (p.llr && p.llr_fmt >= POLAR_LLR_F16) hipLaunchKernelGGL(sc8_decode_kernel<true>, dim3((grid_waves + SC8_WPB - 1) / SC8_WPB), dim3(64 * SC8_WPB), polar_sc8_lds_bytes(p.N), st, p);
+    else hipLaunchKernelGGL(sc8_decode_kernel<false>, dim3((grid_waves + SC8_WPB - 1) / SC8_WPB), dim3(64 * SC8_WPB), polar_sc8_lds_bytes(p.N), st, p);
     return hipGetLastError();
 }
 
@@ -551,7 +570,7 @@ __global__ __launch_bounds__(64) void sc_lat_kernel(PolarScParams p) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int i = i0 + 64 * k + lane;
-                    x[k] = (i < N) ? (p.llr_f32 ? (double)reinterpret_cast<const float *>(p.llr)[(size_t)cw * N + i]
+                    x[k] = (i < N) ? (p.llr_fmt ? llr_load_narrow(p.llr, (size_t)cw * N + i, p.llr_fmt)
                                                 : reinterpret_cast<const double *>(p.llr)[(size_t)cw * N + i]) : 1.0;
                 }
 #pragma unroll

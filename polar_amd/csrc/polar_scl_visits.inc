@@ -97,7 +97,7 @@
                             }
                         } else {
                             if (kind == 2) {
-                                const double *chr = ch_row<ED>(p, cw_of_lane(lane), N);
+                                const double *chr = ch_row<CH_N16>(p, cw_of_lane(lane), N);
                                 for (int e = lig; e < S1; e += GS) {
                                     const unsigned i0 = __brev((unsigned)e) >> (32 - n);
                                     const double a = CH(chr, i0), b = CH(chr, i0 + 1);
@@ -192,7 +192,7 @@
                         const bool in_is_ch = (lam == 1);
                         const bool in_pre = !in_is_ch && p.prefix_q > 0 && 2 * S >= p.prefix_q && phi < 2 * S;
                         // (active lanes are valid ones: codeword g0 + lane / GS)
-                        const double *in0 = in_is_ch ? ch_row<ED>(p, cw_of_lane(lane), N) : nullptr;
+                        const double *in0 = in_is_ch ? ch_row<CH_N16>(p, cw_of_lane(lane), N) : nullptr;
                         const double *pre_cw = in_pre ? p.pre + cw_of_lane(lane) * (size_t)(N - p.prefix_q + 1) : nullptr;
                         const int pin = (in_is_ch || in_pre) ? 0 : pL.get(sh + 1);
                         const size_t istr = in_pre ? 1 : 64;      // prefix layers are contiguous per codeword
@@ -446,7 +446,7 @@
                     size_t istride;
                     const bool in_is_ch = (lam == 1);
                     const bool in_pre = !in_is_ch && p.prefix_q > 0 && 2 * S >= p.prefix_q && phi < 2 * S;
-                    const double *in0 = in_is_ch ? ch_row<ED>(p, cw_of_lane(lane), N) : nullptr;
+                    const double *in0 = in_is_ch ? ch_row<CH_N16>(p, cw_of_lane(lane), N) : nullptr;
                     const double *pre_cw = in_pre ? p.pre + cw_of_lane(lane) * (size_t)(N - p.prefix_q + 1) : nullptr;
                     constexpr bool in_lds = false;          // (LDS inputs were handled above)
                     istride = 64;
