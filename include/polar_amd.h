@@ -137,6 +137,41 @@ int polar_reserve(polar_code_t *h, long B, int L);
 int polar_decode_scl_llr_batch_dev_ev(polar_code_t *h, const double *d_llr, long B, int L, uint8_t *d_out,
                                       double *d_pm, void *stream, void *ev_start, void *ev_stop);
 
+/* ---- list output of decode_scl_llr: every path the list decoder holds at the end of a codeword ----
+ * (no member of the reference's class: its findMostProbablePath, PolarCode.cpp:609-644, returns one path and drops the rest.)
+ * Per codeword, rows r = 0 .. L-1:
+ *   cand[B][L][K]  uint8   information bits of the path in row r, in the reference's order (as `out` of decode_scl_llr)
+ *   pm[B][L]       double  its path metric
+ *   crc_ok[B][L]   uint8   1 = the path passes the handle's CRC (crc == 0: 1 for every active path)
+ *   n_active[B]    int32   paths the decoder holds; fewer than L only when the list never filled (more entries than 2^K words)
+ *   winner[B]      int32   the row decode_scl_llr returns for this codeword, or -1 where the reference returns its never-activated
+ *                          path 0 (no candidate with a finite metric AND a list that never filled: the all-zero word)
+ * Row order: CRC pass before fail, then the smaller metric (+inf last), then the lower path index of the decoder. Rows
+ * n_active .. L-1 are padding: bits 0, pm = +inf, crc_ok = 0. Outside the degenerate rows just described winner is 0.
+ * cand[b][winner[b]] (K zeros for -1) is bit for bit the `out` of polar_decode_scl_llr_batch_fmt for the same row, and
+ * pm[b][winner[b]] bit for bit the d_pm of polar_decode_scl_llr_batch_dev_fmt under polar_set_mode(h, 1) with the batch kernel.
+ * `fmt` = POLAR_LLR_*, with the alignment rules of polar_decode_scl_llr_batch_dev_fmt. 1 <= L <= POLAR_MAX_LIST, any value (the
+ * decoder works on the next power of two of lanes). d_cand / cand is required, the other four outputs may be NULL. POLAR_E_ARG,
+ * before the device is touched: unknown fmt, NULL handle / rows / cand, L out of range, negative B, 16-bit rows at an odd address;
+ * B = 0 is POLAR_OK.
+ * One kernel family serves every call: the LLR-domain batch kernel (mode 1's arithmetic) at its default tuning. polar_set_mode,
+ * polar_set_tuning and the latency threshold do not affect a list call; there is no one-codeword-per-wave form, so a small batch
+ * takes as long as a batch that fills the device once.
+ *   _dev   device pointers, stream-ordered on `stream`, no host synchronisation: one prefix launch (where the code has an
+ *          all-frozen prefix and L >= 3) and one decode launch. It grows the handle's scratch on demand like the other _dev calls;
+ *          polar_reserve's no-allocation promise does NOT cover it (reserve sizes the scratch of decode_scl_llr's kernels only).
+ *   host   host pointers: ONE copy of all B rows in, then per chunk of codewords the launches, a wait and the copies out. The
+ *          chunk (256 MiB of list output: L K + 9 L + 8 bytes per codeword) bounds the device memory of the OUTPUT; the input is
+ *          resident for the whole call. No pipelining, no pinned staging, no latency kernels: a convenience form.
+ * polar_list_find_dev: d_rank[b] = the smallest row r < d_n_active[b] whose K bits equal d_info[b] ([B][K], e.g. the sent word),
+ * or L when there is none — "was the sent word in the list?" without moving the list to the host. All pointers required. */
+int polar_decode_scl_llr_list_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, int L, uint8_t *d_cand, double *d_pm,
+                                        uint8_t *d_crc_ok, int32_t *d_n_active, int32_t *d_winner, void *stream);
+int polar_decode_scl_llr_list_batch(polar_code_t *h, const void *llr, int fmt, long B, int L, uint8_t *cand, double *pm,
+                                    uint8_t *crc_ok, int32_t *n_active, int32_t *winner);
+int polar_list_find_dev(polar_code_t *h, const uint8_t *d_cand, const int32_t *d_n_active, const uint8_t *d_info, long B, int L,
+                        int32_t *d_rank, void *stream);
+
 /* ---- PolarCode::decode_scl_p1 (PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);

@@ -23,6 +23,7 @@ extern "C" {
  *   "lat_max_b"                   largest batch that takes the one-codeword-per-wave kernels (0 = default, -1 = never)
  *   "host_pipe_min_bytes", "host_chunk_bytes", "host_lanes", "host_threads", "host_ramp", "host_prefault"
  *                                 the pipelined host-pointer path (0 = default everywhere)
+ *   "list_chunk_cw"               codewords per output chunk of polar_decode_scl_llr_list_batch (0 = default: 256 MiB of list output)
  *   "multi_timeout_s", "multi_grace_s"    watchdog of a multi-device step and its grace periods
  * Fault injection (libpolar_amd_test.so only; no environment form):
  *   "share_device"                one GPU may be listed several times in a device list (separate contexts, host-side sum)

@@ -46,6 +46,28 @@ def _llr_fmt_code(fmt):
     return int(fmt)
 
 
+def _llr_rows(llr, fmt):
+    """(POLAR_LLR_* code, C-contiguous array) of the LLR rows of decode_scl_llr / decode_scl_llr_list: float32 and float16 arrays
+    travel as they are, fmt="bf16" / "f16" take 16-bit patterns as uint16, anything else is taken as float64."""
+    if fmt is not None:
+        code = _llr_fmt_code(fmt)
+        if code >= LLR_F16:
+            ok = (np.uint16, np.float16) if code == LLR_F16 else (np.uint16,)
+            if not (isinstance(llr, np.ndarray) and llr.dtype in ok):
+                raise PolarError("fmt=%r takes the 16-bit patterns as a uint16 array%s" %
+                                 (fmt, " (or the values as float16)" if code == LLR_F16 else ""))
+            a = np.ascontiguousarray(llr)
+        else:
+            a = np.ascontiguousarray(llr, np.float32 if code == LLR_F32 else np.float64)
+    elif isinstance(llr, np.ndarray) and llr.dtype == np.float32:
+        code, a = LLR_F32, np.ascontiguousarray(llr)
+    elif isinstance(llr, np.ndarray) and llr.dtype == np.float16:
+        code, a = LLR_F16, np.ascontiguousarray(llr)
+    else:
+        code, a = LLR_F64, np.ascontiguousarray(llr, np.float64)
+    return code, a
+
+
 def _rx_flag(receiver):
     if receiver not in RECEIVERS:
         raise PolarError(f"unknown receiver {receiver!r} (supported: {RECEIVERS})")
@@ -422,22 +444,7 @@ class PolarCode:
         the float64 call's on the widened values, bit for bit.
         out (optional): a C-contiguous uint8 [B, K] array to receive the bits (a caller that decodes batch after batch keeps
         one: a fresh 64-MiB array costs its page faults on every call)."""
-        if fmt is not None:
-            code = _llr_fmt_code(fmt)
-            if code >= LLR_F16:
-                ok = (np.uint16, np.float16) if code == LLR_F16 else (np.uint16,)
-                if not (isinstance(llr, np.ndarray) and llr.dtype in ok):
-                    raise PolarError("fmt=%r takes the 16-bit patterns as a uint16 array%s" %
-                                     (fmt, " (or the values as float16)" if code == LLR_F16 else ""))
-                a = np.ascontiguousarray(llr)
-            else:
-                a = np.ascontiguousarray(llr, np.float32 if code == LLR_F32 else np.float64)
-        elif isinstance(llr, np.ndarray) and llr.dtype == np.float32:
-            code, a = LLR_F32, np.ascontiguousarray(llr)
-        elif isinstance(llr, np.ndarray) and llr.dtype == np.float16:
-            code, a = LLR_F16, np.ascontiguousarray(llr)
-        else:
-            code, a = LLR_F64, np.ascontiguousarray(llr, np.float64)
+        code, a = _llr_rows(llr, fmt)
         single = a.ndim == 1
         a2 = a.reshape(-1, self.N)
         if out is None:
@@ -447,6 +454,43 @@ class PolarCode:
         self._chk(self._L.polar_decode_scl_llr_batch_fmt(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(a2.shape[0]),
                                                     C.c_int(list_size), _p(out, _u8p)))
         return out[0] if single else out
+
+    def decode_scl_llr_list(self, llr, list_size, fmt=None):
+        """Every path the list decoder holds at the end of each codeword (polar_decode_scl_llr_list_batch): returns
+        (cand [B, L, K] uint8, pm [B, L] float64, crc_ok [B, L] uint8, n_active [B] int32, winner [B] int32). Rows are ordered
+        CRC pass first, then by metric; rows >= n_active are padding (bits 0, pm = inf, crc_ok = 0); cand[b, winner[b]] is what
+        decode_scl_llr returns (winner = -1: the all-zero word). `llr` and `fmt` as decode_scl_llr; a single row [N] is a batch
+        of one. Any list size 1 .. 64."""
+        code, a = _llr_rows(llr, fmt)
+        a2 = a.reshape(-1, self.N)
+        B, L = a2.shape[0], int(list_size)
+        if not 1 <= L <= 64:
+            raise PolarError("list size %d out of range [1, 64]" % L)
+        cand = np.zeros((B, L, self.K), np.uint8)
+        pm = np.zeros((B, L), np.float64)
+        crc_ok = np.zeros((B, L), np.uint8)
+        n_active = np.zeros(B, np.int32)
+        winner = np.zeros(B, np.int32)
+        self._chk(self._L.polar_decode_scl_llr_list_batch(
+            self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), C.c_int(L), C.c_void_p(cand.ctypes.data),
+            C.c_void_p(pm.ctypes.data), C.c_void_p(crc_ok.ctypes.data), C.c_void_p(n_active.ctypes.data),
+            C.c_void_p(winner.ctypes.data)))
+        return cand, pm, crc_ok, n_active, winner
+
+    def decode_scl_llr_list_dev(self, llr_ptr, fmt, B, list_size, cand_ptr, pm_ptr=0, crc_ok_ptr=0, n_active_ptr=0, winner_ptr=0,
+                                stream=None):
+        """Device-resident form (polar_decode_scl_llr_list_batch_dev): LLRs [B, N] of format `fmt` -> cand uint8 [B, L, K] and,
+        where a pointer is given, pm float64 [B, L], crc_ok uint8 [B, L], n_active int32 [B], winner int32 [B]; asynchronous
+        on `stream`."""
+        self._chk(self._L.polar_decode_scl_llr_list_batch_dev(
+            self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B), C.c_int(list_size), C.c_void_p(cand_ptr),
+            C.c_void_p(pm_ptr), C.c_void_p(crc_ok_ptr), C.c_void_p(n_active_ptr), C.c_void_p(winner_ptr), _stream_ptr(stream)))
+
+    def list_find_dev(self, cand_ptr, n_active_ptr, info_ptr, B, list_size, rank_ptr, stream=None):
+        """rank int32 [B] = the first row < n_active[b] of cand [B, L, K] whose bits equal info [B, K], or L (polar_list_find_dev);
+        device pointers, asynchronous on `stream`."""
+        self._chk(self._L.polar_list_find_dev(self._h, C.c_void_p(cand_ptr), C.c_void_p(n_active_ptr), C.c_void_p(info_ptr),
+                                              C.c_long(B), C.c_int(list_size), C.c_void_p(rank_ptr), _stream_ptr(stream)))
 
     def decode_scl_llr_dev_f32(self, llr_ptr, B, list_size, out_ptr, pm_ptr=0, stream=None):
         """Device-resident float32 LLRs [B, N] -> uint8 [B, K]; asynchronous on `stream`."""

@@ -86,6 +86,29 @@ public:
         check(polar_decode_scl_llr_batch_fmt(_h, llr.data(), llr_format, B, list_size, out.data()));
         return out;
     }
+    // Every path the list decoder holds at the end of each codeword (polar_decode_scl_llr_list_batch; B codewords back to back):
+    // rows ordered CRC pass first, then by metric; rows >= n_active are padding; cand row winner[b] is decode_scl_llr's result
+    // (winner -1: the all-zero word). Any list size 1 .. POLAR_MAX_LIST.
+    struct ListResult {
+        long B = 0;
+        int L = 0, K = 0;
+        std::vector<uint8_t> cand;       // [B][L][K]
+        std::vector<double> pm;          // [B][L]
+        std::vector<uint8_t> crc_ok;     // [B][L]
+        std::vector<int32_t> n_active;   // [B]
+        std::vector<int32_t> winner;     // [B]
+    };
+    ListResult decode_scl_llr_list(const std::vector<double> &llr, uint16_t list_size) {
+        need(llr.size() % _block_length == 0, "decode_scl_llr_list: size must be a multiple of block_length");
+        need(list_size >= 1 && list_size <= POLAR_MAX_LIST, "decode_scl_llr_list: list size out of range");
+        ListResult r;
+        r.B = (long)(llr.size() / _block_length); r.L = list_size; r.K = _info_length;
+        r.cand.resize((size_t)r.B * r.L * r.K); r.pm.resize((size_t)r.B * r.L); r.crc_ok.resize((size_t)r.B * r.L);
+        r.n_active.resize((size_t)r.B); r.winner.resize((size_t)r.B);
+        check(polar_decode_scl_llr_list_batch(_h, llr.data(), POLAR_LLR_F64, r.B, r.L, r.cand.data(), r.pm.data(), r.crc_ok.data(),
+                                              r.n_active.data(), r.winner.data()));
+        return r;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

@@ -215,6 +215,26 @@ __global__ __launch_bounds__(64) void count_errors_kernel(const uint8_t *a, cons
     }
 }
 
+// list output (polar_decode_scl_llr_list_batch_dev): in which row of its list is a given word? One wave per codeword, the lanes
+// stride over the K bytes of a row, one ballot per row; rank_out[b] = the first row r < n_active[b] equal to info[b], or L
+__global__ __launch_bounds__(64) void list_find_kernel(const uint8_t *cand, const int32_t *n_active, const uint8_t *info, long B, int L,
+                                                        int K, int32_t *rank_out) {
+    const int lane = threadIdx.x;
+    for (long c = blockIdx.x; c < B; c += gridDim.x) {
+        int na = n_active[c];
+        na = na < 0 ? 0 : (na > L ? L : na);
+        const uint8_t *want = info + (size_t)c * K;
+        int found = L;
+        for (int r = 0; r < na; ++r) {
+            const uint8_t *row = cand + ((size_t)c * L + r) * (size_t)K;
+            bool diff = false;
+            for (int i = lane; i < K; i += 64) diff |= (row[i] != want[i]);
+            if (__ballot(diff) == 0) { found = r; break; }        // (wave-uniform)
+        }
+        if (lane == 0) rank_out[c] = found;
+    }
+}
+
 // ---- Monte-Carlo round, device side (no host round trip between the (L, Eb/N0) points) ----
 __global__ __launch_bounds__(256) void mc_init_alive_kernel(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < T; i += (long)gridDim.x * 256) alive[i] = t0 + (uint64_t)i * (uint64_t)stride;
@@ -271,5 +291,10 @@ hipError_t polar_launch_mc_count_compact(const uint8_t *decoded, const uint8_t *
 hipError_t polar_launch_count_errors(const uint8_t *a, const uint8_t *b, long B, int K,
                                      unsigned long long *err, uint8_t *flags, hipStream_t st) {
     hipLaunchKernelGGL(count_errors_kernel, dim3(grid_for(B)), dim3(64), 0, st, a, b, B, K, err, flags);
+    return hipGetLastError();
+}
+hipError_t polar_launch_list_find(const uint8_t *cand, const int32_t *n_active, const uint8_t *info, long B, int L, int K,
+                                  int32_t *rank_out, hipStream_t st) {
+    hipLaunchKernelGGL(list_find_kernel, dim3(grid_for(B)), dim3(64), 0, st, cand, n_active, info, B, L, K, rank_out);
     return hipGetLastError();
 }

@@ -28,6 +28,7 @@ int polar_debug_set(polar_code_t *h, const char *key, long value) {
     else if (s == "fail_collective") k.fail_collective = (int)value;
 #endif
     else if (s == "lat_max_b") k.lat_max_b = value;
+    else if (s == "list_chunk_cw") { if (value < 0) return fail(POLAR_E_ARG, "list_chunk_cw must be >= 0"); k.list_chunk_cw = value; }
     else if (s == "host_pipe_min_bytes") k.host_pipe_min_bytes = value;
     else if (s == "host_chunk_bytes") k.host_chunk_bytes = value;
     else if (s == "host_lanes") { if (value < 0 || value > HostPipe::kMaxLanes) return fail(POLAR_E_ARG, "host_lanes must be 0 (default) or 1 .. %d", HostPipe::kMaxLanes); k.host_lanes = value; }

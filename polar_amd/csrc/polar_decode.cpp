@@ -55,6 +55,20 @@ int polar_decode_scl_llr_batch_dev_ev(polar_code_t *h, const double *d_llr, long
 // B rows are allocated; when n_dev != nullptr only the first min(B, *n_dev) exist (count read on the device)
 }  // extern "C"
 
+// all-frozen prefix [0, P): handled cooperatively by the kernel when one codeword owns 32 lanes
+void polar_host::prefix_geometry(const polar_code *h, int gs, int *q_out, int *len_out) {
+    int P = 0;
+    while (P < h->N && h->frozen[P]) ++P;
+    int Q = 0;
+    if (gs >= 4 && h->prefix_on) {
+        if (P >= 256) Q = 256;
+        else { Q = 64; while (Q <= P) Q <<= 1; if (P < 33) Q = 0; }
+        if (Q > h->N / 2) Q = 0;
+    }
+    *q_out = Q;
+    *len_out = Q ? std::min(P, Q) : 0;
+}
+
 int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
                             double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase, int *deferred) {
     if (!h || !d_llr || !d_out) return fail(POLAR_E_ARG, "NULL argument");
@@ -103,18 +117,7 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long 
     if ((rc = h->d_hist_scr.ensure((size_t)grid * 3 * h->W * 64 + 64))) return rc;
     PolarDecodeParams p;
     p.n = h->n; p.N = h->N; p.K = h->K; p.crc = h->crc; p.L = L; p.W = h->W; p.B = B;
-    {   // all-frozen prefix [0, P): handled cooperatively by the kernel when one codeword owns 32 lanes
-        int P = 0;
-        while (P < h->N && h->frozen[P]) ++P;
-        int Q = 0;
-        if (gs >= 4 && h->prefix_on) {
-            if (P >= 256) Q = 256;
-            else { Q = 64; while (Q <= P) Q <<= 1; if (P < 33) Q = 0; }
-            if (Q > h->N / 2) Q = 0;
-        }
-        p.prefix_q = Q;
-        p.prefix_len = Q ? std::min(P, Q) : 0;
-    }
+    prefix_geometry(h, gs, &p.prefix_q, &p.prefix_len);
     p.llr = (const double *)d_llr; p.llr_fmt = llr_fmt; p.p0 = nullptr; p.out = d_out; p.pm_out = d_pm;
     p.frozen = h->d_frozen.p; p.info_rank = h->d_info_rank.p; p.crc_mask = h->d_crc_mask.p; p.tabs = h->d_tabs.p;
     p.ctl = h->d_ctl.p;

@@ -4,6 +4,7 @@
 //   polar_handle.cpp      construction (the reference's constructor work), tables, device upload, getters / setters
 //   polar_decode.cpp      kernel-family dispatch of decode_scl_llr (decode_impl), device-resident entry points, P1 paths, encoder
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
+//   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the pipelined-round scheduler, Monte-Carlo code construction
 //   polar_multi.cpp       multi-device context: RCCL binding, worker threads, watchdog, per-device clones
@@ -253,6 +254,7 @@ struct polar_code {
     DevBuf<uint8_t> d_flags;
     DevBuf<uint32_t> d_list;
     DevBuf<unsigned int> d_count;
+    DevBuf<double> d_list_out;       // host-pointer list call: one chunk of list output (metrics, counts, winners, bits, CRC flags: polar_list.cpp)
     DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never
@@ -280,6 +282,7 @@ struct polar_code {
         long host_threads = 0;         // threads that copy between the caller's memory and the pinned slots (calling thread included)
         long host_ramp = 0;            // -1: no small first chunks (all chunks equal)
         long host_fail_alloc = 0;      // (test hook) the staging slot with this number (1-based) cannot be allocated
+        long list_chunk_cw = 0;        // codewords per output chunk of the host-pointer list call (polar_list.cpp; 0 = default)
         long host_prefault = 0;        // threads that fault the caller's (fresh) output pages in while the first chunks decode (0 = default, -1 = none)
     } knobs;
     // Monte-Carlo engine (device side): alive lists (double-buffered), their lengths, per-round counters
@@ -343,6 +346,8 @@ int upload(DevBuf<T> &d, const std::vector<T> &v) {
 int decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
                 double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase = 0, int *deferred = nullptr);
 bool use_sc_lat(const polar_code *h, long B);
+// the all-frozen prefix the list kernels leave to prefix_kernel for groups of `gs` lanes: block size *Q (0 = none), leaves *len
+void prefix_geometry(const polar_code *h, int gs, int *Q, int *len);
 // (polar_kernels.h repeats the POLAR_LLR_* codes of include/polar_amd.h for the translation units that do not see the public header)
 static_assert(POLAR_LLR_F64 == 0 && POLAR_LLR_F32 == 1 && POLAR_LLR_F16 == 2 && POLAR_LLR_BF16 == 3, "POLAR_LLR_* codes");
 int llr_fmt_check(int fmt, const void *rows);      // POLAR_E_ARG for an unknown POLAR_LLR_* code or 16-bit rows at an odd address (polar_hostpipe.cpp)

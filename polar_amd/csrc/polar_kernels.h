@@ -41,6 +41,17 @@ struct PolarDecodeParams {
     double *tab_scr;             // table mode (GS = 32, exp-domain): per-wave [grid][2][3N] layer-1/-2 value tables, nullptr = off
     uint32_t *var_scr;           //   per-wave [grid][N/32][64] variant nibbles of the paths
 };
+// The list-output launch (polar_launch_decode_llr_list) takes the decode parameters with the list's output pointers BEHIND them: every
+// field above keeps its offset, and the kernels of the other translation units keep their argument block — and with it the
+// offsets of the launch geometry the runtime appends to it, i.e. their machine code — byte for byte. `out` and `pm_out` are not
+// written by that launch. Rows in the order of include/polar_amd.h polar_decode_scl_llr_list_batch_dev.
+struct PolarListParams : PolarDecodeParams {
+    uint8_t *list_cand;          // [B][L][K] device
+    double *list_pm;             // [B][L] device or nullptr
+    uint8_t *list_crc;           // [B][L] device or nullptr
+    int32_t *list_nact;          // [B] device or nullptr
+    int32_t *list_win;           // [B] device or nullptr
+};
 
 size_t polar_decode_lds_bytes(int lds_log, int pipe);
 int polar_decode_waves_per_block(int pipe);
@@ -54,6 +65,8 @@ hipError_t polar_launch_decode_llr_ed1(const PolarDecodeParams &p, int gs, int l
 hipError_t polar_launch_decode_lat(const PolarDecodeParams &p, int gs, bool ed, int blocks, hipStream_t st);
 size_t polar_decode_lat_lds_bytes(int N, int gs, int W);
 hipError_t polar_launch_decode_llr(const PolarDecodeParams &p, int gs, int lds_log, int pipe, int grid, bool ed, hipStream_t st);
+// every surviving path of every codeword (LLR-domain arithmetic, batch geometry, default tuning: LDS_LOG = 3, four waves per block)
+hipError_t polar_launch_decode_llr_list(const PolarListParams &p, int gs, int grid, hipStream_t st);
 hipError_t polar_launch_ed_front(const void *llr, int llr_fmt, double *ech, uint8_t *flags, const double *tabs, int N, long B, const unsigned *n_dev, hipStream_t st);
 hipError_t polar_launch_ed_collect(const uint8_t *flags, long B, const unsigned *n_dev, uint32_t *list, unsigned *count, hipStream_t st);
 
@@ -147,6 +160,9 @@ struct PolarEncodeParams {
 };
 hipError_t polar_launch_encode(const PolarEncodeParams &p, hipStream_t st);
 hipError_t polar_launch_synth(const PolarEncodeParams &p, hipStream_t st);   // BPSK or ASK/BICM by p.constellation
+// rank_out[b] = smallest row r < n_active[b] of cand [B][L][K] whose K bytes equal info [B][K], or L (polar_channel.hip)
+hipError_t polar_launch_list_find(const uint8_t *cand, const int32_t *n_active, const uint8_t *info, long B, int L, int K,
+                                  int32_t *rank_out, hipStream_t st);
 hipError_t polar_launch_count_errors(const uint8_t *a, const uint8_t *b, long B, int K,
                                      unsigned long long *err, uint8_t *mismatch_flags, hipStream_t st);
 // Monte-Carlo round on the device (PolarCode.cpp:728-742, 758-769): alive[i] = t0 + i*stride, *n = T

@@ -98,8 +98,17 @@ __device__ __forceinline__ double ch_narrow(const double *row, size_t i, int fmt
 // the layer visits differ (lat_visit), and the whole state lives in LDS: layers (N - 1) GS doubles (element j of slot s at
 // [(j GS + s)]: a wave access is 64 consecutive doubles), the converted channel, the partial-sum and history words. A lone wave of the
 // batch kernel pays an HBM round trip per dependent access of its scratch layers and evaluates every element of a layer serially.
+#if defined(POLAR_ED_TU) && POLAR_ED_TU == 4
+// the list-output unit: the same kernel text with the finish of polar_scl_finish.inc that writes every surviving path, under a
+// symbol of its own (the instantiations <GS, 3, 0, false> also exist in unit 0, with the winner-only finish)
+#define POLAR_LIST_OUT 1
+#define scl_decode_llr_kernel scl_decode_llr_list_kernel
+#define POLAR_KPARAMS PolarListParams
+#else
+#define POLAR_KPARAMS PolarDecodeParams
+#endif
 template <int GS, int LDS_LOG, int PIPE, bool ED, int NL = 0, int LAT = 0>
-__global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_llr_kernel(PolarDecodeParams p) {
+__global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_llr_kernel(POLAR_KPARAMS p) {
     // ED: exp-domain node arithmetic (see f_node_e); the channel values at p.llr are then in stored form
     // (ed_front_kernel) and every codeword whose decisions are not safely reproduced is reported in p.flags
     // PIPE=1: one wave per block (8 waves/CU, register double-buffering); PIPE=0: four independent
@@ -616,11 +625,12 @@ __global__ __launch_bounds__(256) void prefix_kernel(PolarDecodeParams p, int st
     }
 }
 
-// This file is compiled four times (polar_amd/build.py): POLAR_ED_TU = 0 instantiates the LLR-domain kernels and
+// This file is compiled five times (polar_amd/build.py): POLAR_ED_TU = 0 instantiates the LLR-domain kernels and
 // the small helper kernels, POLAR_ED_TU = 1 the exp-domain kernels of the groups of 4, 8, 16 and 64 lanes, POLAR_ED_TU = 2 the
 // exp-domain list of 32 — translation units that build in parallel, that one with its own scheduler options
 // (max-memory-clause strategy + the AMDGPU register-pressure trackers: +2.2 ... 3.8 % on the headline kernel, -11 % on the
-// groups of 8: build.py) —, POLAR_ED_TU = 3 the exp-domain one-codeword-per-wave (LAT) kernels.
+// groups of 8: build.py) —, POLAR_ED_TU = 3 the exp-domain one-codeword-per-wave (LAT) kernels, POLAR_ED_TU = 4 the
+// LLR-domain batch kernels with the list-output finish (every group size, default tuning only: DESIGN.md §8e).
 #ifndef POLAR_ED_TU
 #define POLAR_ED_TU 0
 #endif
@@ -776,7 +786,29 @@ size_t polar_decode_lat_lds_bytes(int N, int gs, int W) {
 }
 #endif
 
-#if POLAR_ED_TU == 2
+#if POLAR_ED_TU == 4
+template <int GS>
+static hipError_t launch_list(const PolarListParams &p, int grid, hipStream_t st) {
+    // (the sizes of polar_decode_lds_bytes(3, 0) / polar_decode_waves_per_block(0), which live in unit 0)
+    constexpr int wpb = 4;
+    constexpr size_t lds = 324 * 8 + (size_t)wpb * ((size_t)((2u << 3) - 1) * 64 * 8 + 128 * 8 + 128);
+    hipLaunchKernelGGL((scl_decode_llr_kernel<GS, 3, 0, false>), dim3(grid / wpb), dim3(64 * wpb), lds, st, p);
+    return hipGetLastError();
+}
+hipError_t polar_launch_decode_llr_list(const PolarListParams &p, int gs, int grid, hipStream_t st) {
+    if (!p.list_cand || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
+    switch (gs) {
+        case 1: return launch_list<1>(p, grid, st);
+        case 2: return launch_list<2>(p, grid, st);
+        case 4: return launch_list<4>(p, grid, st);
+        case 8: return launch_list<8>(p, grid, st);
+        case 16: return launch_list<16>(p, grid, st);
+        case 32: return launch_list<32>(p, grid, st);
+        case 64: return launch_list<64>(p, grid, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+#elif POLAR_ED_TU == 2
 hipError_t polar_launch_decode_llr_ed1_gs32(const PolarDecodeParams &p, int lds_log, int pipe, int grid, hipStream_t st) {
     return launch_gs<32, true>(p, lds_log, pipe, grid, st);
 }

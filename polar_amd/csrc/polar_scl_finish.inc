@@ -49,6 +49,66 @@
         // was never activated, its info array still holds the zeros of initializeDataStructures (PolarCode.cpp:195-230).
         // (Found by tools/fuzz_parity.py; this read used to return whatever an earlier codeword left in the slot.)
         const bool win_active = __shfl((int)active, gbase + win, 64) != 0;
+#ifdef POLAR_LIST_OUT
+        {   // ---------------- list output: every surviving path instead of the winner alone (DESIGN.md §8e) ----------------
+            static_assert(!ED && !LAT && !PIPE, "the list-output unit instantiates the LLR-domain batch kernel only");
+            (void)pm_win;
+            // Row of a path = how many lanes of its group come before it: active paths first, then CRC pass before fail, then the
+            // smaller metric (+inf last), then the lower lane — the winner selection's own tie-break. A comparison count over the
+            // group: GS - 1 shuffles of (metric, class) per lane, no sort network. Inactive lanes take the rows behind the active
+            // ones in lane order: the padded rows n_active .. L-1 are theirs.
+            const bool ok = active && pass;
+            const int cls = active ? (ok ? 0 : 1) : 2;
+            const double km = active ? pm : __builtin_inf();
+            int rank = 0;
+            for (int j = 1; j < GS; ++j) {
+                const int oi = (lig + j) & (GS - 1);
+                const double om = shfl_d(km, gbase + oi);
+                const int oc = __shfl(cls, gbase + oi, 64);
+                rank += (oc < cls || (oc == cls && (om < km || (om == km && oi < lig)))) ? 1 : 0;
+            }
+            const int n_act = __popcll((__ballot(active) >> gbase) & gmask);
+            const int win_row = __shfl(rank, gbase + win, 64);
+            // every active path walks its OWN word list into its own column of g_tb
+            if (active) {
+                int cur = lig;
+                for (int w = Wused - 1; w >= 0; --w) {
+                    g_tb[(size_t)w * CST + POLAR_CL] = g_hist[(size_t)w * CST + POLAR_CGB + cur];
+                    cur = (int)(g_horg[(size_t)w * CST + POLAR_CGB + cur] & (GS - 1));
+                }
+            }
+            wave_mem_fence();
+            // path by path: the lanes of the group stride over the K bytes of ONE row (consecutive bytes per store instruction), the
+            // words come from that path's column
+            const size_t row0 = (size_t)(valid ? cw : 0) * (size_t)L;
+            for (int j = 0; j < GS; ++j) {
+                const int rj = __shfl(rank, gbase + j, 64);
+                const bool aj = __shfl((int)active, gbase + j, 64) != 0;
+                if (valid && rj < L) {
+                    uint8_t *dst = p.list_cand + (row0 + (size_t)rj) * (size_t)K;
+                    for (int b = lig; b < K; b += GS) {
+                        uint8_t v = 0;
+                        if (aj) {
+                            const unsigned r = p.info_rank[b];
+                            v = (uint8_t)((g_tb[(size_t)(r >> 5) * CST + POLAR_CGB + j] >> (r & 31)) & 1u);
+                        }
+                        dst[b] = v;
+                    }
+                }
+            }
+            if (valid && rank < L) {
+                if (p.list_pm) p.list_pm[row0 + (size_t)rank] = km;
+                if (p.list_crc) p.list_crc[row0 + (size_t)rank] = ok ? (uint8_t)1 : (uint8_t)0;
+            }
+            if (valid && lig == 0) {
+                if (p.list_nact) p.list_nact[cw] = n_act;
+                // (the reference's l_p = 0 when no candidate has a finite metric: a row like any other if that path is active, no row
+                // at all — the all-zero word — if the list never filled)
+                if (p.list_win) p.list_win[cw] = win_active ? win_row : -1;
+            }
+            wave_mem_fence();
+        }
+#else
         if (valid) {
 #if !defined(POLAR_PROFILE) && !defined(POLAR_SLOTHIST)
             if (p.pm_out && lig == 0) p.pm_out[cw] = pm_win;
@@ -77,6 +137,7 @@
             else if (valid && lig == 0 && ((guard >> gbase) & gmask) != 0) p.flags[cw] = 1;
         }
         wave_mem_fence();
+#endif  // POLAR_LIST_OUT
 #ifdef POLAR_MARGIN
         if (valid && lig == 0 && K >= 16) {      // (overwrites the first 16 info bytes: this build measures, it does not decode)
             double *o = reinterpret_cast<double *>(p.out + (size_t)cw * K);
