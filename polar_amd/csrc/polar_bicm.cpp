@@ -67,12 +67,7 @@ int demap_host(int constellation, const void *y, int y_f32, int N, long B, doubl
 }
 
 int decode_args(const polar_code *h, int constellation, const void *y, double n0, long B, int L, const uint8_t *out) {
-    if (!h || !y || !out) return fail(POLAR_E_ARG, "NULL argument");
-    int rc;
-    if ((rc = bicm_check(constellation, n0))) return rc;
-    if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
-    if (B < 0) return fail(POLAR_E_ARG, "negative batch");
-    return POLAR_OK;
+    return check_args(h && y && out, L, B, [&] { return bicm_check(constellation, n0); });
 }
 
 int decode_dev(polar_code_t *h, int constellation, const void *d_y, int y_f32, double n0, long B, int L, uint8_t *d_out,

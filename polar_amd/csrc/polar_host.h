@@ -2,7 +2,9 @@
 // (`struct polar_code`), its device buffers, and the functions the translation units share.
 //
 //   polar_handle.cpp      construction (the reference's constructor work), tables, device upload, getters / setters
-//   polar_decode.cpp      kernel-family dispatch of decode_scl_llr (decode_impl), device-resident entry points, P1 paths, encoder
+//   polar_decode.cpp      decode_scl_llr on the device: the family choice (choose_family), one launcher per kernel family behind
+//                         decode_impl, the device-resident entry points, P1 paths, encoder
+//   polar_mlc.cpp         MLC receiver: checks, parameter fill, dispatch of the multistage SC kernels, its entry points
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
 //   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
@@ -339,20 +341,59 @@ int upload(DevBuf<T> &d, const std::vector<T> &v) {
     if (v.size()) HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return POLAR_OK;
 }
+// The argument checks the entry points share, in the order the ABI pins: the pointers (`ptrs_set`: none is null), `mid` (the entry
+// point's own llr_fmt_check, bicm_check or mlc_check), the list size (kNoList: the call has none), the batch
+constexpr int kNoList = 1;
+inline int check_args(bool ptrs_set, int L, long B, const std::function<int()> &mid = nullptr) {
+    if (!ptrs_set) return fail(POLAR_E_ARG, "NULL argument");
+    if (int rc = mid ? mid() : POLAR_OK) return rc;
+    if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
+    return B < 0 ? fail(POLAR_E_ARG, "negative batch") : POLAR_OK;
+}
+// What the per-wave state scratch of a launch may take: at most 24 GiB, and at most half of what the device has free plus what the
+// handle already holds for it (a smaller or busy GPU runs fewer persistent waves instead of failing with POLAR_E_NOMEM)
+inline size_t scratch_budget(const polar_code *h) {
+    size_t budget = (size_t)24 << 30, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, (free_b + h->d_llr_scr.cap * sizeof(double)) / 2);
+    return std::max(budget, (size_t)64 << 20);
+}
+// the persistent grid of the P1 and MLC kernels: `want` waves, each with `per_wave` bytes of scratch — halved until the scratch is there
+template <typename Ensure>
+int grid_that_fits(const polar_code *h, long want, size_t per_wave, Ensure ensure, int *grid_out) {
+    // (the budget is a driver query — hipMemGetInfo takes milliseconds: asked only when the scratch the handle holds is too small)
+    long grid = want;
+    if ((size_t)want * per_wave > h->d_llr_scr.cap * sizeof(double)) grid = std::max<long>(1, std::min<long>(want, (long)(scratch_budget(h) / per_wave)));
+    for (;;) {
+        const int rc = ensure((int)grid);
+        if (rc != POLAR_E_NOMEM || grid <= 64) { *grid_out = (int)grid; return rc; }
+        (void)hipGetLastError();
+        grid /= 2;
+    }
+}
+
 // polar_decode.cpp
-// phase (list size 1 with the one-codeword-per-wave kernel only): 0 = everything; 1 = the decode kernel alone — the caller
-// looks at the flag words itself and runs phase 2 (work list + general kernel over the flagged codewords) only when one is
-// set; *deferred reports whether phase 1 really left the fallback out
+// the kernel families of decode_scl_llr, and which one a call takes on this handle (no side effects)
+enum class Family { Sc8, ScLat, ListLat, BatchLlr, BatchEd };
+Family choose_family(const polar_code *h, long B, int L, bool want_pm);
+// phase (the one-codeword-per-wave kernels only): 0 = everything; 1 = the decode kernel alone — the caller looks at the flags
+// *deferred names (none: the fallback ran; d_flag_words + 4; d_flags) and runs phase 2, the fallback pass, only when one is set
+enum class Deferred { None, FlagWords, FlagBytes };
 int decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long B, const unsigned int *n_dev, int L, uint8_t *d_out,
-                double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase = 0, int *deferred = nullptr);
-bool use_sc_lat(const polar_code *h, long B);
-// the all-frozen prefix the list kernels leave to prefix_kernel for groups of `gs` lanes: block size *Q (0 = none), leaves *len
-void prefix_geometry(const polar_code *h, int gs, int *Q, int *len);
+                double *d_pm, void *stream, void *ev_start, void *ev_stop, int phase = 0, Deferred *deferred = nullptr);
+// Launch geometry of the batch kernel: G codewords (groups of gs lanes) per wave, `grid` waves in blocks of wpb, each with big * 64 doubles
+// and 2 * cwords * 64 words of scratch. tuned: the handle's tuning and the small-batch rule; else the default. false: the LDS does not fit.
+struct BatchGeometry { int gs, G, wpc, lds_log, pipe, wpb, grid; size_t big, cwords; };
+bool batch_geometry(const polar_code *h, long B, int L, bool tuned, BatchGeometry &g);
+int ensure_batch_scratch(polar_code *h, const BatchGeometry &g);          // d_llr_scr, d_c_scr, d_hist_scr for g.grid waves
+// the ONE place the decode parameters are filled (tables, scratch, work counter; no prefix, optional pointers null): a caller adds its own
+void base_params(const polar_code *h, int L, long B, PolarDecodeParams &p);
+// the all-frozen prefix the batch kernels leave to prefix_kernel for groups of `gs` lanes: p.prefix_q / prefix_len / pre (d_pre grown)
+int prefix_params(polar_code *h, int gs, PolarDecodeParams &p);
 // (polar_kernels.h repeats the POLAR_LLR_* codes of include/polar_amd.h for the translation units that do not see the public header)
 static_assert(POLAR_LLR_F64 == 0 && POLAR_LLR_F32 == 1 && POLAR_LLR_F16 == 2 && POLAR_LLR_BF16 == 3, "POLAR_LLR_* codes");
 int llr_fmt_check(int fmt, const void *rows);      // POLAR_E_ARG for an unknown POLAR_LLR_* code or 16-bit rows at an odd address (polar_hostpipe.cpp)
 void fill_enc(const polar_code *h, PolarEncodeParams &p);
-// MLC receiver (polar_kernels_mlc.hip): *cid = the constellation without POLAR_RX_MLC, after the checks of include/polar_amd.h
+// polar_mlc.cpp — MLC receiver (polar_kernels_mlc.hip): *cid = the constellation without POLAR_RX_MLC, after the checks of include/polar_amd.h
 int mlc_check(const polar_code *h, int constellation, int *cid);
 void fill_mlc(const polar_code *h, int cid, double snr_db, PolarMlcParams &p);   // snr_db: sigma / n0 of the sweep's axis
 int mlc_decode_launch(polar_code *h, int cid, const double *d_y, double n0, long B, const unsigned int *n_dev, double *d_out,

@@ -34,6 +34,17 @@ void polar_host::hostpipe_release(polar_code *h) {
     delete hp;
 }
 
+// codewords the batch kernel holds at a time at its default 16 waves per CU
+static long resident_codewords(const polar_code *h, int L) { return (long)h->num_cu * 16 * (64 / pow2ceil(L)); }
+// symbol rows (sym != nullptr) are demapped on `st` into the context's own LLR rows, which the decode then reads instead
+static int demap_rows(polar_code *c, const SymRows *sym, long B, hipStream_t st, const void **d_rows, int *rows_fmt) {
+    if (!sym) return POLAR_OK;
+    const double *d_llr = nullptr;
+    if (int rc = bicm_front(c, sym->cid, sym->n0, *d_rows, *rows_fmt, B, st, &d_llr)) return rc;
+    *d_rows = d_llr; *rows_fmt = POLAR_LLR_F64;
+    return POLAR_OK;
+}
+
 static int hostpipe_ensure(polar_code_t *h, size_t in_slot, size_t out_slot, int lanes, int threads) {
     if (!h->hpipe) h->hpipe = new HostPipe;
     HostPipe *hp = h->hpipe;
@@ -170,11 +181,8 @@ static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_fmt, 
         polar_code *c = l ? hp->ctx[l] : h;
         const void *d_rows = hp->d_in[slot];
         int rows_fmt = llr_fmt;
-        if (sym) {          // the demap launch precedes the decode on the lane's stream; each lane's context owns its LLR rows
-            const double *d_llr = nullptr;
-            if ((rc = bicm_front(c, sym->cid, sym->n0, d_rows, llr_fmt, nb, st, &d_llr))) break;
-            d_rows = d_llr; rows_fmt = POLAR_LLR_F64;
-        }
+        // (the demap launch precedes the decode on the lane's stream; each lane's context owns its LLR rows)
+        if ((rc = demap_rows(c, sym, nb, st, &d_rows, &rows_fmt))) break;
         if ((rc = decode_impl(c, d_rows, rows_fmt, nb, nullptr, L, hp->d_out[slot], nullptr, st, nullptr, nullptr))) break;
         e = hipMemcpyAsync(hp->pin_out[slot], hp->d_out[slot], (size_t)nb * row_out, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipEventRecord(hp->done[slot], st);
@@ -188,13 +196,10 @@ static int host_decode_pipelined(polar_code_t *h, const void *llr, int llr_fmt, 
 }
 
 int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const SymRows *sym, long B, int L, uint8_t *out) {
-    if (!h || !llr || !out) return fail(POLAR_E_ARG, "NULL argument");
-    if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
-    if (B < 0) return fail(POLAR_E_ARG, "negative batch");
-    if (B == 0) return POLAR_OK;
+    int rc = check_args(h && llr && out, L, B);
+    if (rc || B == 0) return rc;
     DevGuard dg_;
-    int rc = ensure_device(h, dg_);
-    if (rc) return rc;
+    if ((rc = ensure_device(h, dg_))) return rc;
     // Symbol rows: the thresholds and chunk sizes below were fitted to LLR bytes, so they are applied to the LLR bytes the symbols
     // stand for (B * N doubles): a batch takes the form — zero-copy, one copy, pipelined, and the same chunks — that the LLR path
     // takes for this B. They were not re-measured for the narrower rows.
@@ -203,7 +208,6 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
     const size_t esz = sym ? sizeof(double) : polar_llr_esz(llr_fmt);
     const size_t in_bytes = (size_t)B * h->N * esz, out_bytes = (size_t)B * h->K;
     const size_t copy_bytes = sym ? (size_t)B * sym->M * polar_llr_esz(llr_fmt) : in_bytes;          // what travels
-    const int mode = h->knobs.mode_override >= 0 ? h->knobs.mode_override : h->mode;
     if (h->hpipe) h->hpipe->last_chunks = 0;
     {
         const polar_code::Knobs &kn = h->knobs;
@@ -214,7 +218,7 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
         // 13.2 against 15.3 .. 17.7 ms. Measured crossovers: L = 1 32 MiB; L = 2 (the LLR-domain 2-lane kernel: the slowest launches)
         // 1 GiB; L = 3 .. 8 half a GiB of LLRs or one full round of resident waves, whichever comes first (N = 1024, L = 8, 65536
         // float rows = 256 MiB = two rounds: 12.0 ms pipelined, 17.7 in one copy); larger lists half a GiB or two rounds.
-        const long resident_cw = (long)h->num_cu * 16 * (64 / pow2ceil(L));
+        const long resident_cw = resident_codewords(h, L);
         const bool pays = L == 1 ? in_bytes >= ((size_t)32 << 20) : L == 2 ? in_bytes >= ((size_t)1 << 30)
                                  : (in_bytes >= ((size_t)512 << 20) || B >= (L <= 8 ? 1 : 2) * resident_cw);
         const size_t min_bytes = kn.host_pipe_min_bytes > 0 ? (size_t)kn.host_pipe_min_bytes : (pays ? 0 : ~(size_t)0);
@@ -225,18 +229,18 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
             // 128 MiB of doubles), 128 MiB of doubles or floats in between (three lanes x 16384 float rows); at least four
             // full-size chunks per batch
             const long fill_cw = 8192L * 2048 / h->N;
-            const bool fills = L > 1 && (long)h->num_cu * 16 * (64 / pow2ceil(L)) <= fill_cw;
+            const bool fills = L > 1 && resident_cw <= fill_cw;
             size_t cb = kn.host_chunk_bytes > 0 ? (size_t)kn.host_chunk_bytes : (L == 1 ? (size_t)64 << 20 : fills ? (size_t)fill_cw * h->N * esz : (size_t)128 << 20);
             if (kn.host_chunk_bytes <= 0) cb = std::min(cb, std::max<size_t>(in_bytes / 4, (size_t)8 << 20));
             const long chunk_cw = std::max<long>(8, (long)(cb / ((size_t)h->N * esz)) / 8 * 8);
             // decode lanes: HIP multiplexes its streams onto four hardware queues, two streams on one queue take turns — two
             // lanes for list size 1 and for the lists whose full-size chunk fills the device, three in between
             int lanes = (int)kn.host_lanes;
-            if (lanes <= 0) lanes = (L == 1 || (long)h->num_cu * 16 * (64 / pow2ceil(L)) <= chunk_cw) ? 2 : 3;
+            if (lanes <= 0) lanes = (L == 1 || resident_cw <= chunk_cw) ? 2 : 3;
             // small first chunks (host_decode_pipelined) unless one full-size chunk already fills the device: the list-of-32
             // kernel runs such a chunk as ONE round of resident waves, and three more launches cost it more than the early start
             // returns (headline, 65536 codewords: 0.87 of the device-resident rate with them, 0.90 .. 0.93 without)
-            const bool ramp = kn.host_ramp > 0 || (kn.host_ramp == 0 && (L == 1 || (long)h->num_cu * 16 * (64 / pow2ceil(L)) > chunk_cw));
+            const bool ramp = kn.host_ramp > 0 || (kn.host_ramp == 0 && (L == 1 || resident_cw > chunk_cw));
             const int threads = kn.host_threads > 0 ? (int)std::min<long>(kn.host_threads, 64) : std::max(1, std::min(8, usable_cpus() / 2));
             if (B > chunk_cw) {
                 bool no_staging = false;
@@ -247,7 +251,7 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
             }
         }
     }
-    if (L == 1 && mode != 1 && use_sc_lat(h, B) && B <= 64) {
+    if (choose_family(h, B, L, false) == Family::ScLat && B <= 64) {          // (zero-copy: the latency kernel reads pinned host memory)
         if (h->pin_in_cap < in_bytes) {
             if (h->pin_in) (void)hipHostFree(h->pin_in);
             h->pin_in = nullptr; h->pin_in_cap = 0;
@@ -267,20 +271,16 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
         memcpy(h->pin_in, llr, copy_bytes);
         const void *d_rows = h->pin_in_dev;
         int rows_fmt = llr_fmt;
-        if (sym) {          // demap first (the kernel reads the mapped symbols), then the latency kernel on the LLR rows in HBM
-            const double *d_llr = nullptr;
-            if ((rc = bicm_front(h, sym->cid, sym->n0, d_rows, llr_fmt, B, nullptr, &d_llr))) return rc;
-            d_rows = d_llr; rows_fmt = POLAR_LLR_F64;
-        }
-        int deferred = 0;
+        if ((rc = demap_rows(h, sym, B, nullptr, &d_rows, &rows_fmt))) return rc;          // (the latency kernel then reads LLR rows in HBM)
+        Deferred deferred = Deferred::None;
         h->lat_flag_bytes = h->pin_out_dev + out_bytes;
         rc = decode_impl(h, d_rows, rows_fmt, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 1, &deferred);
         h->lat_flag_bytes = nullptr;
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));
-        bool any = !deferred;
+        bool any = false;
         for (long i = 0; i < B && !any; ++i) any = h->pin_out[out_bytes + i] != 0;
-        if (any && deferred) {
+        if (any && deferred != Deferred::None) {
             if ((rc = decode_impl(h, d_rows, rows_fmt, B, nullptr, L, h->pin_out_dev, nullptr, nullptr, nullptr, nullptr, 2, nullptr))) return rc;
             HIP_TRY(hipStreamSynchronize(nullptr));
         }
@@ -297,23 +297,19 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
         if ((rc = h->d_out.ensure(out_bytes))) return rc;
         HIP_TRY(hipMemcpy(d_stage, llr, copy_bytes, hipMemcpyHostToDevice));
         d_in = d_stage;
-        if (sym) {
-            const double *d_llr = nullptr;
-            if ((rc = bicm_front(h, sym->cid, sym->n0, d_stage, llr_fmt, B, nullptr, &d_llr))) return rc;
-            d_in = d_llr; llr_fmt = POLAR_LLR_F64;
-        }
+        if ((rc = demap_rows(h, sym, B, nullptr, &d_in, &llr_fmt))) return rc;
     }
-    int deferred = 0;
+    Deferred deferred = Deferred::None;
     if ((rc = decode_impl(h, d_in, llr_fmt, B, nullptr, L, h->d_out.p, nullptr, nullptr, nullptr, nullptr, 1, &deferred))) return rc;
-    if (deferred) {
+    if (deferred != Deferred::None) {
         HIP_TRY(hipMemcpy(out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost));          // (waits for the kernel)
         bool any = false;
-        if (deferred == 1) {                 // list size 1: flag words
+        if (deferred == Deferred::FlagWords) {
             const size_t nfw = (size_t)(B + 31) / 32;
             std::vector<unsigned int> fw(nfw);
             HIP_TRY(hipMemcpy(fw.data(), h->d_flag_words.p + 4, nfw * sizeof(unsigned int), hipMemcpyDeviceToHost));
             for (unsigned int w : fw) any |= (w != 0);
-        } else {                             // small lists: flag bytes
+        } else {
             std::vector<uint8_t> fb((size_t)B);
             HIP_TRY(hipMemcpy(fb.data(), h->d_flags.p, (size_t)B, hipMemcpyDeviceToHost));
             for (uint8_t b : fb) any |= (b != 0);

@@ -53,8 +53,14 @@ struct PolarListParams : PolarDecodeParams {
     int32_t *list_win;           // [B] device or nullptr
 };
 
-size_t polar_decode_lds_bytes(int lds_log, int pipe);
-int polar_decode_waves_per_block(int pipe);
+// launch geometry of scl_decode_llr_kernel: waves per block, LDS per block, and what a path column keeps in the per-wave scratch —
+// the elements of the layers above 2^lds_log, the words of the big partial-sum layers (S >= 64)
+static inline int polar_decode_waves_per_block(int pipe) { return pipe ? 1 : 4; }
+static inline size_t polar_decode_lds_bytes(int lds_log, int pipe) {
+    return 324 * 8 + (size_t)polar_decode_waves_per_block(pipe) * ((size_t)((2u << lds_log) - 1) * 64 * 8 + 128 * 8 + 128);
+}
+static inline size_t polar_decode_big(int N, int lds_log) { return N > (2 << lds_log) ? (size_t)(N - (2 << lds_log)) : 0; }
+static inline size_t polar_decode_cwords(int N) { return N >= 128 ? (size_t)(N / 32 - 2) : 0; }
 hipError_t polar_launch_prefix(const PolarDecodeParams &p, bool ed, double *ech_out, hipStream_t st);
 hipError_t polar_launch_prefix_ed0(const PolarDecodeParams &p, double *ech_out, hipStream_t st);
 hipError_t polar_launch_prefix_ed1(const PolarDecodeParams &p, double *ech_out, hipStream_t st);

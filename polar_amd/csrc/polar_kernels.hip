@@ -710,12 +710,6 @@ hipError_t polar_launch_ed_collect(const uint8_t *flags, long B, const unsigned 
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------
-int polar_decode_waves_per_block(int pipe) { return pipe ? 1 : 4; }
-size_t polar_decode_lds_bytes(int lds_log, int pipe) {
-    return 324 * 8 + (size_t)polar_decode_waves_per_block(pipe) * ((size_t)((2u << lds_log) - 1) * 64 * 8 + 128 * 8 + 128);
-}
-
 #endif  // !POLAR_ED_TU
 
 template <int GS, bool ED>
@@ -780,18 +774,16 @@ hipError_t polar_launch_decode_lat(const PolarDecodeParams &p, int gs, bool ed, 
     return hipErrorInvalidValue;
 }
 size_t polar_decode_lat_lds_bytes(int N, int gs, int W) {
-    const int cwords = (N >= 128) ? (N / 32 - 2) : 0;
     // tables + exchange buffers + converted channel + layers + partial-sum and history words (one column per path)
-    return 324 * 8 + (128 * 8 + 128) + (size_t)N * 8 + (size_t)N * gs * 8 + ((size_t)2 * cwords + (size_t)3 * W) * gs * 4 + 64;
+    return 324 * 8 + (128 * 8 + 128) + (size_t)N * 8 + (size_t)N * gs * 8 + (2 * polar_decode_cwords(N) + (size_t)3 * W) * gs * 4 + 64;
 }
 #endif
 
 #if POLAR_ED_TU == 4
 template <int GS>
 static hipError_t launch_list(const PolarListParams &p, int grid, hipStream_t st) {
-    // (the sizes of polar_decode_lds_bytes(3, 0) / polar_decode_waves_per_block(0), which live in unit 0)
-    constexpr int wpb = 4;
-    constexpr size_t lds = 324 * 8 + (size_t)wpb * ((size_t)((2u << 3) - 1) * 64 * 8 + 128 * 8 + 128);
+    const int wpb = polar_decode_waves_per_block(0);
+    const size_t lds = polar_decode_lds_bytes(3, 0);
     hipLaunchKernelGGL((scl_decode_llr_kernel<GS, 3, 0, false>), dim3(grid / wpb), dim3(64 * wpb), lds, st, p);
     return hipGetLastError();
 }

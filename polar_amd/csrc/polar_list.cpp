@@ -7,57 +7,30 @@
 namespace {
 
 int list_check(const polar_code *h, const void *llr, int fmt, long B, int L, const uint8_t *cand) {
-    if (!h || !llr || !cand) return fail(POLAR_E_ARG, "NULL argument");
-    int rc = llr_fmt_check(fmt, llr);
-    if (rc) return rc;
-    if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
-    if (B < 0) return fail(POLAR_E_ARG, "negative batch");
-    return POLAR_OK;
+    return check_args(h && llr && cand, L, B, [&] { return llr_fmt_check(fmt, llr); });
 }
 
 // (arguments checked, B > 0, the handle's device current)
 int list_launch(polar_code *h, const void *d_llr, int fmt, long B, int L, uint8_t *d_cand, double *d_pm, uint8_t *d_crc_ok,
                 int32_t *d_n_active, int32_t *d_winner, hipStream_t st) {
-    const int gs = pow2ceil(L), G = 64 / gs;
-    const int lds_log = 3, wpb = 4, wpc = 16;
-    if (polar_decode_lds_bytes(lds_log, 0) > h->lds_per_block) return fail(POLAR_E_UNSUPPORTED, "the list kernel's LDS does not fit this device");
-    const long groups = (B + G - 1) / G;
-    int grid = (int)std::min<long>(groups, (long)h->num_cu * wpc);
-    grid = ((grid + wpb - 1) / wpb) * wpb;          // whole blocks
-    const int SL = 1 << lds_log;
-    const size_t big = (h->N > 2 * SL) ? (size_t)(h->N - 2 * SL) : 0;
-    const size_t cwords = (h->N >= 128) ? (size_t)(h->N / 32 - 2) : 0;
+    BatchGeometry g;
+    if (!batch_geometry(h, B, L, false, g)) return fail(POLAR_E_UNSUPPORTED, "the list kernel's LDS does not fit this device");
     int rc;
     // the per-wave state scratch (the decode's own buffers, grown on demand); a device too full for it runs fewer persistent waves
-    for (;;) {
-        rc = h->d_llr_scr.ensure((size_t)grid * big * 64 + 64);
-        if (rc != POLAR_E_NOMEM || grid <= wpb) break;
+    while ((rc = ensure_batch_scratch(h, g)) == POLAR_E_NOMEM && g.grid > g.wpb) {
         (void)hipGetLastError();
-        grid = std::max(wpb, (grid / 2 / wpb) * wpb);
+        g.grid = std::max(g.wpb, (g.grid / 2 / g.wpb) * g.wpb);
     }
     if (rc) return rc;
-    if ((rc = h->d_c_scr.ensure((size_t)grid * 2 * cwords * 64 + 64))) return rc;
-    if ((rc = h->d_hist_scr.ensure((size_t)grid * 3 * h->W * 64 + 64))) return rc;
     if ((rc = h->d_work.ensure(1))) return rc;
     PolarListParams p;
-    p.n = h->n; p.N = h->N; p.K = h->K; p.crc = h->crc; p.L = L; p.W = h->W; p.B = B;
-    prefix_geometry(h, gs, &p.prefix_q, &p.prefix_len);
-    p.llr = (const double *)d_llr; p.llr_fmt = fmt; p.p0 = nullptr; p.out = nullptr; p.pm_out = nullptr;
-    p.frozen = h->d_frozen.p; p.info_rank = h->d_info_rank.p; p.crc_mask = h->d_crc_mask.p; p.tabs = h->d_tabs.p;
-    p.ctl = h->d_ctl.p;
-    p.pre = nullptr;
-    p.flags = nullptr; p.cw_list = nullptr; p.cw_count = nullptr; p.n_dev = nullptr;
-    p.tab_scr = nullptr; p.var_scr = nullptr;
-    if (p.prefix_q) {
-        if ((rc = h->d_pre.ensure((size_t)B * (size_t)(h->N - p.prefix_q + 1)))) return rc;
-        p.pre = h->d_pre.p;
-    }
-    p.llr_scr = h->d_llr_scr.p; p.c_scr = h->d_c_scr.p; p.hist_scr = h->d_hist_scr.p;
-    p.work = h->d_work.p;
+    base_params(h, L, B, p);
+    p.llr = (const double *)d_llr; p.llr_fmt = fmt;
+    if ((rc = prefix_params(h, g.gs, p))) return rc;
     p.list_cand = d_cand; p.list_pm = d_pm; p.list_crc = d_crc_ok; p.list_nact = d_n_active; p.list_win = d_winner;
     HIP_TRY(hipMemsetAsync(p.work, 0, sizeof(unsigned int), st));
     if (p.prefix_q) HIP_TRY(polar_launch_prefix(p, false, nullptr, st));
-    HIP_TRY(polar_launch_decode_llr_list(p, gs, grid, st));
+    HIP_TRY(polar_launch_decode_llr_list(p, g.gs, g.grid, st));
     return POLAR_OK;
 }
 
@@ -108,12 +81,10 @@ int polar_decode_scl_llr_list_batch(polar_code_t *h, const void *llr, int fmt, l
 
 int polar_list_find_dev(polar_code_t *h, const uint8_t *d_cand, const int32_t *d_n_active, const uint8_t *d_info, long B, int L,
                         int32_t *d_rank, void *stream) {
-    if (!h || !d_cand || !d_n_active || !d_info || !d_rank) return fail(POLAR_E_ARG, "NULL argument");
-    if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
-    if (B <= 0) return B == 0 ? POLAR_OK : fail(POLAR_E_ARG, "negative batch");
+    int rc = check_args(h && d_cand && d_n_active && d_info && d_rank, L, B);
+    if (rc || B == 0) return rc;
     DevGuard dg_;
-    int rc = ensure_device(h, dg_);
-    if (rc) return rc;
+    if ((rc = ensure_device(h, dg_))) return rc;
     HIP_TRY(polar_launch_list_find(d_cand, d_n_active, d_info, B, L, h->K, d_rank, (hipStream_t)stream));
     return POLAR_OK;
 }
