@@ -177,8 +177,10 @@ int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double 
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);
 
 /* ---- PolarM decode_sc_p1 (PolarCode.m:290-295, 870-895): SC on p1 = P(bit = 1) ----
- * out are doubles, as MATLAB returns them: 0 / 1, and 0.5 where a leaf probability is exactly 0.5
- * (sign(0) = 0 at PolarCode.m:873). */
+ * out are doubles, as MATLAB returns them: 0 / 1, 0.5 where a leaf probability is exactly 0.5
+ * (sign(0) = 0 at PolarCode.m:873), and NaN where a leaf probability is NaN (sign(NaN) = NaN: vnop,
+ * PolarCode.m:893-895, divides 0 by 0 when its inputs contradict each other with certainty, e.g. p1 = 0, 1
+ * on a pair whose first bit is frozen; once a decision is NaN the partial sums carry it to later leaves). */
 int polar_decode_sc_p1(polar_code_t *h, const double *p1 /*[N]*/, double *out /*[K]*/);
 int polar_decode_sc_p1_batch(polar_code_t *h, const double *p1, long B, double *out);
 

@@ -556,11 +556,11 @@ int orc_decode_scl_p1(void *h, const double *p1, const double *p0, int L, uint8_
  * (PolarCode.m:76-83 apply bit_reversed_order to the channel vector before sorting), and the
  * recursion pairs adjacent inputs y(1:2:end), y(2:2:end) exactly like PolarC's layers, so the
  * PolarC tables are used as they are.  Returns u (decisions) and x (re-encoded partial sums);
- * a leaf with y == 0.5 yields 0.5 (sign(0) = 0), as in MATLAB. */
+ * a leaf with y == 0.5 yields 0.5 (sign(0) = 0) and a NaN leaf (0 / 0 in vnop) yields NaN, as in MATLAB. */
 static void orc_m_decode(const double *y, const uint8_t *fz, int len, double *u, double *x) {
     if (len == 1) {                                   /* :872-878 */
         if (fz[0]) { x[0] = 0; }
-        else { double t = 1 - 2 * y[0]; double sg = (double)((t > 0) - (t < 0)); x[0] = (1 - sg) / 2; }
+        else { double t = 1 - 2 * y[0]; double sg = (t != t) ? t : (double)((t > 0) - (t < 0)); x[0] = (1 - sg) / 2; }   /* sign(NaN) is NaN */
         u[0] = x[0];
         return;
     }

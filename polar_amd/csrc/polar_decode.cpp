@@ -353,7 +353,7 @@ int polar_decode_scl_p1(polar_code_t *h, const double *p1, const double *p0, int
     return polar_decode_scl_p1_batch(h, p1, p0, 1, L, out);
 }
 
-// PolarM decode_sc_p1 (PolarCode.m:290-295): out are doubles like MATLAB's (0.5 when a leaf is exactly 0.5)
+// PolarM decode_sc_p1 (PolarCode.m:290-295): out are doubles like MATLAB's (0.5 when a leaf is exactly 0.5, NaN when a leaf is NaN)
 int polar_decode_sc_p1_batch(polar_code_t *h, const double *p1, long B, double *out) {
     int rc = check_args(h && p1 && out, kNoList, B);
     if (rc || B == 0) return rc;

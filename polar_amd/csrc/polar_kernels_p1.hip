@@ -325,11 +325,18 @@ __global__ __launch_bounds__(64) void scl_decode_p1_kernel(PolarDecodeParams p) 
             if (ok > key || (ok == key && oi < kidx)) { key = ok; kidx = oi; }
         }
         const int win = (key > 0.0) ? kidx : 0;
+        // No path beats 0 (sigma == 0 somewhere: every probability is 0) AND the list never filled (more list entries than 2^K
+        // paths): the reference's l_p = 0 is a path that was never activated, its info array still holds the zeros of
+        // initializeDataStructures (PolarCode.cpp:195-230) — while this lane's column of g_hist holds another codeword's words.
+        const bool win_active = __shfl((int)active, gbase + win, 64) != 0;
         if (valid) {
             for (int b = lig; b < K; b += GS) {
-                unsigned r = p.info_rank[b];
-                uint32_t wd = g_hist[(size_t)(r >> 5) * 64 + gbase + win];
-                p.out[(size_t)cw * K + b] = (uint8_t)((wd >> (r & 31)) & 1u);
+                uint8_t bit = 0;
+                if (win_active) {
+                    const unsigned r = p.info_rank[b];
+                    bit = (uint8_t)((g_hist[(size_t)(r >> 5) * 64 + gbase + win] >> (r & 31)) & 1u);
+                }
+                p.out[(size_t)cw * K + b] = bit;
             }
         }
         wave_mem_fence();
@@ -337,7 +344,7 @@ __global__ __launch_bounds__(64) void scl_decode_p1_kernel(PolarDecodeParams p) 
 }
 
 // ---- PolarM decode_sc_p1: one lane per codeword, natural recursion made iterative -----------
-// y layers and "hard" partial sums are doubles as in MATLAB (a leaf with y == 0.5 yields 0.5).
+// y layers and "hard" partial sums are doubles as in MATLAB (a leaf with y == 0.5 yields 0.5, a NaN leaf — 0 / 0 in vnop — NaN).
 __global__ __launch_bounds__(64) void sc_p1_kernel(PolarScP1Params p) {
     const int lane = threadIdx.x;
     const int n = p.n, N = p.N, K = p.K;
@@ -379,7 +386,7 @@ __global__ __launch_bounds__(64) void sc_p1_kernel(PolarScP1Params p) {
                 }
                 double x;
                 if (p.frozen[phi]) x = 0.0;                                              // :875-876
-                else { const double tt = 1 - 2 * leaf; x = (1 - (double)((tt > 0) - (tt < 0))) / 2; }   // :873
+                else { const double tt = 1 - 2 * leaf; x = (1 - ((tt != tt) ? tt : (double)((tt > 0) - (tt < 0)))) / 2; }   // :873 (sign(NaN) is NaN)
                 gu[(size_t)phi * 64 + lane] = x;
                 if ((phi & 1) == 0) gxl[(size_t)1 * 64 + lane] = x;
                 else {
@@ -463,7 +470,7 @@ __global__ __launch_bounds__(64) void sc_p1_lat_kernel(PolarScP1Params p) {
             } else leaf = ly[1];
             double x;
             if (fz) x = 0.0;                                                         // :875-876
-            else { const double tt = 1 - 2 * leaf; x = (1 - (double)((tt > 0) - (tt < 0))) / 2; }   // :873
+            else { const double tt = 1 - 2 * leaf; x = (1 - ((tt != tt) ? tt : (double)((tt > 0) - (tt < 0)))) / 2; }   // :873 (sign(NaN) is NaN)
             if (lane == 0) lu[phi] = x;
             if ((phi & 1) == 0) {
                 xprev = x;

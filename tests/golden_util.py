@@ -87,7 +87,9 @@ def both_kernels(g, decode):
     g.debug_set("lat_max_b", 1 << 40)
     b = decode()
     g.debug_set("lat_max_b", 0)
-    assert (a == b).all(), "the one-codeword-per-wave kernel and the batch kernel disagree"
+    # (decode_sc_p1 returns doubles and NaN where MATLAB does: a NaN in the same place in both is agreement)
+    same = np.array_equal(a, b, equal_nan=True) if np.issubdtype(a.dtype, np.floating) else (a == b).all()
+    assert same, "the one-codeword-per-wave kernel and the batch kernel disagree"
     return a
 
 

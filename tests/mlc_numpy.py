@@ -210,7 +210,7 @@ def polar_decode(y, f):
     M = y.shape[-1]
     if M == 1:
         if f[0] == 0:
-            # x = (1 - sign(1 - 2y)) / 2 (:873) with the sign of decode_sc_p1's kernels, (t > 0) - (t < 0): a NaN leaf decides
+            # x = (1 - sign(1 - 2y)) / 2 (:873) with the sign of the MLC kernels, (t > 0) - (t < 0): a NaN leaf decides
             # 0.5 (MATLAB's sign(NaN) is NaN; either way the value matches no label bit in the demapper of the next layer)
             t = 1 - 2 * y
             x = (1 - ((t > 0).astype(np.float64) - (t < 0).astype(np.float64))) / 2

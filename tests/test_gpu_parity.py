@@ -4,18 +4,11 @@ import numpy as np
 import pytest
 
 from golden_util import both_kernels, both_l1_kernels
+from p1_rows import pair as _pair          # (oracle, device code) with the same construction
 
 pytestmark = pytest.mark.gpu
 
 
-def _pair(n, K, crc, srand=1):
-    import ctypes as C
-    import polar_amd
-    from oracle_lib import Oracle
-    o = Oracle(n, K, 0.32, crc, srand=srand)
-    C.CDLL(None).srand(C.c_uint(srand))
-    g = polar_amd.PolarCode(n, K, 0.32, crc)
-    return o, g
 
 
 CODES = [(5, 16, 4), (8, 128, 0), (9, 256, 0), (10, 512, 8), (11, 1024, 0), (11, 1024, 16)]
