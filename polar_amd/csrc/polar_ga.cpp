@@ -23,8 +23,6 @@ int check_device() {
     return POLAR_OK;
 }
 
-double sigma_of(double snr_db) { return std::sqrt(1.0 / 2) * std::pow(10.0, -snr_db / 20); }   // Constellation.m:251
-
 // y grid of the integrals: y_k = -ymax + k * dy, k = 0 .. P-1, P = floor(2 ymax / dy + 1e-9) + 1
 PolarGaGrid make_grid(double n0, double ymax, double dy) {
     PolarGaGrid g;
@@ -58,7 +56,7 @@ int capacity(int kind, int c, const double *snr_db, int n, double *out) {
             const double n0 = 1.0 / 2 * std::pow(10.0, -snr_db[i] / 10);
             g[i] = make_grid(n0, std::min(10000.0, 1.0 + 3 + 3 * std::sqrt(n0)), std::sqrt(n0) * 0.001);
         } else {
-            const double s = sigma_of(snr_db[i]);
+            const double s = sigma_of_snr_db(snr_db[i]);
             g[i] = make_grid(s * s, pmax + 6 * s + 1, s * (kind == 0 ? 0.1 : 0.01));
         }
         if (!(g[i].P > 0 && g[i].P < (1L << 40))) return fail(POLAR_E_ARG, "SNR %g dB gives an unusable grid", snr_db[i]);
@@ -105,7 +103,7 @@ int polarized_counts(int c, const double *snr_db, int n, long num_sym, uint64_t 
     const int nb = polar_const_nbits(c);
     const size_t per = (size_t)nb * POLAR_GA_BINS * 2;
     std::vector<double> sg(n), n0(n);
-    for (int i = 0; i < n; ++i) { sg[i] = sigma_of(snr_db[i]); n0[i] = sg[i] * sg[i]; }
+    for (int i = 0; i < n; ++i) { sg[i] = sigma_of_snr_db(snr_db[i]); n0[i] = sg[i] * sg[i]; }
     DevBuf<double> d_s;
     DevBuf<unsigned long long> d_c;
     struct Guard { DevBuf<double> &a; DevBuf<unsigned long long> &b; ~Guard() { a.release(); b.release(); } } guard{d_s, d_c};

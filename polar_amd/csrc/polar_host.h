@@ -8,7 +8,8 @@
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
 //   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
-//   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the pipelined-round scheduler, Monte-Carlo code construction
+//   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction
+//   polar_mc_schedule.h   the schedule of the pipelined rounds alone (standard library only: tests/test_mc_schedule.py runs it on a CPU)
 //   polar_multi.cpp       multi-device context: RCCL binding, worker threads, watchdog, per-device clones
 //   polar_debug.cpp       measurement knobs (include/polar_amd_debug.h); fault injection only with -DPOLAR_TEST_HOOKS
 #pragma once
@@ -328,6 +329,11 @@ struct DevGuard {
 };
 
 inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+// the POLAR_CONST_* ids (include/polar_synth.h): the range of the ASK constellations — BPSK's id lies inside it —, and the same without BPSK
+inline bool is_ask_constellation(int c) { return c >= POLAR_CONST_ASK4_GRAY && c <= POLAR_CONST_ASK16_SP; }
+inline bool is_ask_not_bpsk(int c) { return is_ask_constellation(c) && c != POLAR_CONST_BPSK; }
+// noise of the ASK workloads at an SNR in dB (main_MC_CC_Comparison.m:88-92, PolarCode.m:170, Constellation.m:251); n0 = sigma^2
+inline double sigma_of_snr_db(double snr_db) { return std::sqrt(1.0 / 2) * std::pow(10.0, -snr_db / 20); }
 
 // polar_handle.cpp
 int derive_tables(polar_code *h);

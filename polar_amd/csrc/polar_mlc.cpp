@@ -20,7 +20,7 @@ void polar_host::fill_mlc(const polar_code *h, int cid, double snr_db, PolarMlcP
     p.M = h->N / p.nb;
     while ((1 << p.m) < p.M) ++p.m;
     p.constellation = cid;
-    p.sigma = std::sqrt(1.0 / 2) * std::pow(10.0, -snr_db / 20);        // main_MC_CC_Comparison.m:90
+    p.sigma = sigma_of_snr_db(snr_db);                                  // main_MC_CC_Comparison.m:90
     p.n0 = p.sigma * p.sigma;
     p.cnorm = polar_const_norm(cid);
     p.stride = 1;

@@ -124,7 +124,7 @@ class Mex:
         owned = [p for p, a in zip(prhs, (cmd,) + args) if not isinstance(a, MxValue)]
         arr = (C.c_void_p * len(prhs))(*prhs)
         out = (C.c_void_p * max(nlhs, 1))()
-        eid, emsg = C.create_string_buffer(256), C.create_string_buffer(1024)
+        eid, emsg = C.create_string_buffer(1024), C.create_string_buffer(1024)     # (fm_call fills BOTH up to its one `cap`, zero padding included)
         try:
             t0 = time.perf_counter()
             rc = self.L.fm_call(nlhs, out, len(prhs), arr, eid, emsg, 1024)
