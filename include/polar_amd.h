@@ -406,7 +406,7 @@ int polar_set_tuning(polar_code_t *h, int waves_per_cu, int lds_log);
  * Environment overrides (measurement and tests only) are read ONCE, when a handle is created, and validated — no entry
  * point calls getenv afterwards: POLAR_MODE=<0|1|2> replaces the handle's mode (any other value: creation fails);
  * POLAR_SC_NO_FOLD=1 makes the list-size-1 kernel decode a permuted, converted copy of the batch (its round-2 front pass)
- * instead of reading the caller's rows in place; POLAR_NO_TABLES=1, POLAR_NO_RCCL=1, POLAR_FORCE_RCCL=1. Results do not
+ * instead of reading the caller's rows in place; POLAR_NO_TABLES=1, POLAR_NO_HEAD=1, POLAR_NO_RCCL=1, POLAR_FORCE_RCCL=1. Results do not
  * depend on any of them. */
 int polar_set_mode(polar_code_t *h, int mode);
 /* how many unfrozen leaves the handle classified as weak at creation (BEC(1/2) capacity below 1e-3; see above). Codes with

@@ -19,6 +19,8 @@ extern "C" {
  * Measurement knobs (both libraries; results never depend on them):
  *   "mode_override" -1|0|1|2      replaces polar_set_mode's value (-1 = none); POLAR_MODE in the environment at creation
  *   "sc_no_fold", "no_tables", "no_fuse_front", "no_prefix"     alternative (older) forms of single passes, for A/B timing
+ *   "no_head"                     lists of 17 .. 32 in one phase: no 4-lane head in front of the list kernel (POLAR_NO_HEAD at creation)
+ *   "head_min_b"                  smallest batch that takes the head (0 = default: from 16 codewords per resident wave on)
  *   "no_rccl", "force_rccl"       counter reduction of the single-process multi-device driver (drops its cached context)
  *   "lat_max_b"                   largest batch that takes the one-codeword-per-wave kernels (0 = default, -1 = never)
  *   "host_pipe_min_bytes", "host_chunk_bytes", "host_lanes", "host_threads", "host_ramp", "host_prefault"
@@ -34,10 +36,11 @@ extern "C" {
  * the handle's per-device contexts and extra decode lanes (they carry a copy of the knobs). */
 int polar_debug_set(polar_code_t *h, const char *key, long value);
 /* polar_debug_get(h, key): "allocs" (hipMalloc calls of all handles' scratch so far), "comm_inits", "weak_leaves",
- * "mode_override", "last_rounds", "last_round_max_per_device", "worker_threads_started", "multi_poisoned",
+ * "mode_override", "head_phi" (hand-over leaf of the handle's last decode_scl_llr launch, 0 = decoded in one phase), "last_rounds", "last_round_max_per_device", "worker_threads_started", "multi_poisoned",
  * "round_us_first|min|median|max|count" (steps of the handle's last sweep), "host_chunks", "host_chunk_cw", "host_lanes",
  * "host_threads", "host_us_copy_in|wait|copy_out|total" (the last pipelined host-pointer call), "test_hooks" (1 in the test
- * build); -1 = unknown key. */
+ * build); -1 = unknown key. Test build only: "head_check" reads the hand-over records of the handle's last two-phase decode back
+ * and returns how many codewords did not arrive with the planned paths (0 = the premise holds; -2 = no records to read). */
 long polar_debug_get(const polar_code_t *h, const char *key);
 /* number of ncclCommInitAll calls made by this library so far (the communicators of a device list are cached on the handle) */
 int polar_debug_comm_inits(void);

@@ -4,6 +4,9 @@
 // -DPOLAR_TEST_HOOKS (libpolar_amd_test.so, what the GPU tests of the failure protocol load).
 #include "polar_multi.h"
 #include "polar_amd_debug.h"
+#ifdef POLAR_TEST_HOOKS
+#include "polar_head_plan.h"
+#endif
 
 extern "C" {
 
@@ -16,6 +19,8 @@ int polar_debug_set(polar_code_t *h, const char *key, long value) {
     if (s == "mode_override") { if (value < -1 || value > 2) return fail(POLAR_E_ARG, "mode_override must be -1 (none), 0, 1 or 2"); k.mode_override = (int)value; }
     else if (s == "sc_no_fold") k.sc_no_fold = value != 0;
     else if (s == "no_tables") k.no_tables = value != 0;
+    else if (s == "no_head") k.no_head = value != 0;
+    else if (s == "head_min_b") { if (value < 0) return fail(POLAR_E_ARG, "head_min_b must be >= 0 (0 = default)"); k.head_min_b = value; }
     else if (s == "no_fuse_front") k.no_fuse_front = value != 0;
     else if (s == "no_prefix") h->prefix_on = (value == 0);          // (the all-frozen prefix decoded leaf by leaf by the list kernel itself)
     // (the cached streams / communicators / worker threads of the last device list were built under the old setting)
@@ -63,6 +68,30 @@ long polar_debug_get(const polar_code_t *h, const char *key) {
     }
     if (s == "weak_leaves") return h->weak_leaves;
     if (s == "mode_override") return h->knobs.mode_override;
+    if (s == "head_phi") return h->last_head_phi;
+#ifdef POLAR_TEST_HOOKS
+    if (s == "head_check") {
+        // The premise of the two-phase decode, checked on what the head really left: row 2 of every record of the handle's last
+        // two-phase call is read back and held against the plan (head_record_ok: no path killed, the top lanes, t) -> the number of
+        // codewords that break it; -2: the last call left no records to read.
+        if (!h->last_head_phi || h->last_head_b <= 0 || !h->d_head_rec.p) return -2;
+        int P = 0;
+        while (P < h->N && h->frozen[P]) ++P;
+        const int Q = P >= 256 ? 256 : (P < 33 ? 0 : (P < 64 ? 64 : (P < 128 ? 128 : 256)));        // (prefix_params, which also allocates)
+        const HeadPlan hp = head_plan(h->frozen.data(), h->n, Q, std::min(P, Q), h->N / 2);
+        if (hp.phi_h != h->last_head_phi) return -3;
+        std::vector<unsigned long long> rows2((size_t)h->last_head_b * 4);
+        const size_t pitch = hp.record_words() * sizeof(unsigned long long);
+        if (hipMemcpy2D(rows2.data(), 32, h->d_head_rec.p + 2 * 4, pitch, 32, (size_t)h->last_head_b, hipMemcpyDeviceToHost) != hipSuccess) return -4;
+        long bad = 0;
+        for (long b = 0; b < h->last_head_b; ++b) {
+            unsigned long long r[4];
+            for (int a = 0; a < 4; ++a) r[a] = rows2[(size_t)b * 4 + a];
+            bad += head_record_ok(hp, r) ? 0 : 1;
+        }
+        return bad;
+    }
+#endif
     if (s == "last_rounds") return h->last_rounds;
     if (s == "last_round_max_per_device") return h->last_round_max_per_device;
     if (s == "worker_threads_started") return h->worker_threads_started;

@@ -2,6 +2,7 @@
 // decode_impl, the device-resident entry points, the probability-domain members of the class surface, encoder / workload generation.
 // Reference: PolarCode::decode_scl_llr (PolarCode.cpp:130-148), decode_scl_p1 (:110-128), encode (:60-91).
 #include "polar_host.h"
+#include "polar_head_plan.h"
 
 namespace {
 
@@ -150,7 +151,7 @@ int decode_batch_ed(Call &c) {
     const long B = c.B;
     int rc;
     if ((rc = prefix_params(h, g.gs, p))) return rc;
-    HIP_TRY(hipMemsetAsync(p.work, 0, sizeof(unsigned int), c.st));
+    HIP_TRY(hipMemsetAsync(p.work, 0, 2 * sizeof(unsigned int), c.st));          // (the second word: phase A of the two-phase form)
     if ((rc = h->d_ech.ensure((size_t)B * h->N))) return rc;
     if ((rc = h->d_flags.ensure((size_t)B))) return rc;
     if ((rc = h->d_list.ensure((size_t)B))) return rc;
@@ -172,7 +173,32 @@ int decode_batch_ed(Call &c) {
         pp.llr = (const double *)c.d_llr; pp.llr_fmt = c.llr_fmt;
         HIP_TRY(polar_launch_prefix(pp, true, h->d_ech.p, c.st));
     } else if (pe.prefix_q) HIP_TRY(polar_launch_prefix(pe, true, nullptr, c.st));
+    // Two phases (polar_head_plan.h): up to the third unfrozen leaf a codeword has at most 4 paths — those leaves go through the
+    // 4-lane instantiation, 16 codewords a wave, which leaves a record per codeword; the list of 32 starts there. Same stream, same
+    // scratch (the phases are sequential), a work counter each. Table mode starts with the build at N/2 when the hand-over lies in
+    // the second quarter (the walk has no table of the first build then), so the hand-over stays below N/2.
+    HeadPlan hp;
+    if (g.gs == 32 && p.prefix_q > 0) hp = head_plan(h->frozen.data(), h->n, p.prefix_q, p.prefix_len, h->N / 2);
+    const long head_min_b = h->knobs.head_min_b ? h->knobs.head_min_b : (long)h->num_cu * 16 * 16;
+    const bool two_phase = head_use(hp, g.lds_log == 3 && !g.pipe, B, head_min_b, h->knobs.no_head);
+    h->last_head_phi = two_phase ? hp.phi_h : 0;
+    h->last_head_b = two_phase && !c.n_dev ? B : 0;
+    PolarHeadParams ph;
+    if (two_phase) {
+        if ((rc = h->d_head_rec.ensure((size_t)B * hp.record_words()))) return rc;
+        static_cast<PolarDecodeParams &>(ph) = pe;
+        ph.head_rec = h->d_head_rec.p; ph.head_phi = hp.phi_h; ph.head_t = hp.t; ph.head_rows = hp.rows();
+        ph.head_llr_mask = hp.llr_mask; ph.head_c_mask = hp.c_mask;
+    }
     if (c.ev_start) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_start, c.st));
+    if (two_phase) {
+        PolarHeadParams pa = ph;
+        pa.L = HeadPlan::kPaths; pa.work = p.work + 1; pa.tab_scr = nullptr; pa.var_scr = nullptr; pa.out = nullptr; pa.pm_out = nullptr;
+        const long waves_a = (B + 15) / 16;
+        const int grid_a = (int)std::min<long>(g.grid, ((waves_a + g.wpb - 1) / g.wpb) * g.wpb);
+        HIP_TRY(polar_launch_decode_head_export(pa, grid_a, c.st));
+        HIP_TRY(polar_launch_decode_head_import(ph, g.grid, c.st));
+    } else
     HIP_TRY(polar_launch_decode_llr(pe, g.gs, g.lds_log, g.pipe, g.grid, true, c.st));
     if (c.ev_stop) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_stop, c.st));
     HIP_TRY(polar_launch_ed_collect(h->d_flags.p, B, c.n_dev, h->d_list.p, h->d_count.p, c.st));
@@ -275,7 +301,8 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long 
     if (rc || B == 0) return rc;
     DevGuard dg_;
     if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = h->d_work.ensure(1))) return rc;
+    if ((rc = h->d_work.ensure(2))) return rc;
+    h->last_head_phi = 0; h->last_head_b = 0;
     const Family fam = choose_family(h, B, L, d_pm != nullptr);
     Call c{h, d_llr, llr_fmt, B, n_dev, L, d_out, d_pm, (hipStream_t)stream, ev_start, ev_stop, phase, deferred, {}, {}};
     // (every family but one ends in a fallback pass of the batch kernel: the small lists in LLR-domain arithmetic flag nothing)
@@ -452,6 +479,16 @@ int polar_reserve(polar_code_t *h, long B, int L) {
         if (!rc && l <= 8) rc = polar_decode_scl_llr_batch_dev(h, llr.p, 1, l, out.p, nullptr, nullptr);
         if (!rc && l == 1) rc = polar_decode_scl_llr_batch_dev(h, llr.p, B, l, out.p, pm.p, nullptr);
         if (!rc && l == 1) rc = polar_decode_scl_llr_batch_dev(h, llr.p + 1, B, l, out.p, nullptr, nullptr);
+    }
+    // the hand-over records of the two-phase list of 32, whatever the knobs and the batch threshold let the decode above do: a
+    // later call within (B, L) that does take the head (another "no_head" / "head_min_b") must not allocate either
+    if (!rc && top >= 32) {
+        PolarDecodeParams pp;
+        base_params(h, 32, B, pp);
+        if (!(rc = prefix_params(h, 32, pp)) && pp.prefix_q > 0) {
+            const HeadPlan hp = head_plan(h->frozen.data(), h->n, pp.prefix_q, pp.prefix_len, h->N / 2);
+            if (hp.phi_h > 0 && hp.window >= kHeadMinWindow) rc = h->d_head_rec.ensure((size_t)B * hp.record_words());
+        }
     }
     hipError_t e = hipDeviceSynchronize();
     llr.release(); out.release(); pm.release();

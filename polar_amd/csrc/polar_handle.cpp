@@ -257,6 +257,7 @@ int read_env_knobs(polar_code *h) {
     }
     h->knobs.sc_no_fold = on("POLAR_SC_NO_FOLD");
     h->knobs.no_tables = on("POLAR_NO_TABLES");
+    h->knobs.no_head = on("POLAR_NO_HEAD");
     h->knobs.no_rccl = on("POLAR_NO_RCCL");
     h->knobs.force_rccl = on("POLAR_FORCE_RCCL");
     return POLAR_OK;
@@ -368,7 +369,7 @@ void polar_destroy(polar_code_t *h) {
     h->d_slot_n.release();
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
-    h->d_sc_ops.release(); h->d_sc_lat_ops.release(); h->d_flag_words.release(); h->d_var_scr.release(); h->d_tab_scr.release();
+    h->d_sc_ops.release(); h->d_sc_lat_ops.release(); h->d_flag_words.release(); h->d_var_scr.release(); h->d_tab_scr.release(); h->d_head_rec.release();
     delete h;
 }
 

@@ -242,6 +242,9 @@ struct polar_code {
     DevBuf<uint16_t> d_order, d_info_rank;
     DevBuf<uint32_t> d_crc_mask, d_ctl, d_sc_ops, d_sc_lat_ops, d_var_scr;
     DevBuf<double> d_tab_scr;
+    DevBuf<unsigned long long> d_head_rec;   // two-phase list of 32: the hand-over records [B][rows][4] (polar_head_plan.h)
+    int last_head_phi = 0;           //   hand-over leaf of the last decode_scl_llr call, 0 = one phase (polar_debug_get "head_phi")
+    long last_head_b = 0;            //   ... and how many records it left (0: rows alive on the device only, Monte-Carlo): polar_debug_get "head_check"
     DevBuf<unsigned int> d_flag_words;
     DevBuf<double> d_llr_scr, d_tabs, d_pre;
     DevBuf<uint32_t> d_c_scr, d_hist_scr;
@@ -266,6 +269,8 @@ struct polar_code {
         int mode_override = -1;      // POLAR_MODE=<0|1|2>: replaces `mode`
         bool sc_no_fold = false;     // POLAR_SC_NO_FOLD: list size 1 decodes a permuted, converted copy (front pass)
         bool no_tables = false;      // POLAR_NO_TABLES: list of 17..32 without the layer-1/2 value tables
+        bool no_head = false;        // POLAR_NO_HEAD: list of 17..32 in one phase (no 4-lane head, polar_head_plan.h)
+        long head_min_b = 0;         //   smallest batch that takes the head (0 = default: 16-codeword waves fill the device)
         bool no_fuse_front = false;  // (hook) exp-domain lists: separate conversion pass in front of the prefix kernel (the round-3 path)
         bool no_rccl = false;        // POLAR_NO_RCCL: multi-device counters summed on the host
         bool force_rccl = false;     // POLAR_FORCE_RCCL: RCCL even with one device

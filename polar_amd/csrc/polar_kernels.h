@@ -53,6 +53,18 @@ struct PolarListParams : PolarDecodeParams {
     int32_t *list_win;           // [B] device or nullptr
 };
 
+// The two-phase list decode (polar_head_plan.h) takes the decode parameters with the hand-over BEHIND them, like the list output:
+// the kernels of the other translation units keep their argument block. Phase A (polar_launch_decode_head_export: the groups of
+// 4 lanes, L = 4) decodes the leaves up to head_phi and writes the records, phase B (polar_launch_decode_head_import: the list of
+// 32) starts there. Same scratch, same geometry; each phase has its own work counter.
+struct PolarHeadParams : PolarDecodeParams {
+    unsigned long long *head_rec; // [B][head_rows][4] device: HeadPlan's record
+    int head_phi, head_t, head_rows;
+    uint32_t head_llr_mask, head_c_mask;
+};
+hipError_t polar_launch_decode_head_export(const PolarHeadParams &p, int grid, hipStream_t st);
+hipError_t polar_launch_decode_head_import(const PolarHeadParams &p, int grid, hipStream_t st);
+
 // launch geometry of scl_decode_llr_kernel: waves per block, LDS per block, and what a path column keeps in the per-wave scratch —
 // the elements of the layers above 2^lds_log, the words of the big partial-sum layers (S >= 64)
 static inline int polar_decode_waves_per_block(int pipe) { return pipe ? 1 : 4; }

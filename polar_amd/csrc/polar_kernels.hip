@@ -36,7 +36,17 @@
 #define PROF(i) { u64 t_ = __builtin_readcyclecounter(); prof_acc[i] += t_ - prof_t; prof_t = t_; }
 #define PROF_OUT if (lane == 0 && p.pm_out) { for (int i_ = 0; i_ < 24; ++i_) atomicAdd((u64 *)p.pm_out + i_, prof_acc[i_]); }
 #define PROF_CNT(i, v) { prof_acc[i] += (u64)(v); }
+// the few-path head: cycles of the leaf loop before the leaf the tool names in word 32 of its buffer -> [22], of the
+// whole loop -> [23] (tools/phase_profile.py prints the share). Like PROF_OUT, which adds its 24 words there, this takes p.pm_out for
+// the TOOL's buffer — at least 64 64-bit words, zeroed —, never a caller's metric array: an instrumented build measures, it does not
+// serve decodes that ask for path metrics.
+#define PROF_HEAD_DECL const int prof_head_phi = p.pm_out ? (int)((const u64 *)p.pm_out)[32] : 0; const u64 prof_head_t0 = prof_t; bool prof_head_open = prof_head_phi > 0;
+#define PROF_HEAD(phi_) if (prof_head_open && (phi_) >= prof_head_phi) { prof_acc[22] += __builtin_readcyclecounter() - prof_head_t0; prof_head_open = false; }
+#define PROF_HEAD_END prof_acc[23] += __builtin_readcyclecounter() - prof_head_t0;
 #else
+#define PROF_HEAD_DECL
+#define PROF_HEAD(phi_)
+#define PROF_HEAD_END
 #define PROF_DECL
 #define PROF(i)
 #define PROF_CNT(i, v)
@@ -104,8 +114,19 @@ __device__ __forceinline__ double ch_narrow(const double *row, size_t i, int fmt
 #define POLAR_LIST_OUT 1
 #define scl_decode_llr_kernel scl_decode_llr_list_kernel
 #define POLAR_KPARAMS PolarListParams
+#elif defined(POLAR_ED_TU) && (POLAR_ED_TU == 5 || POLAR_ED_TU == 6)
+// the two-phase units (polar_head_plan.h): the same kernel text with a compile-time hand-over mode, under a symbol
+// of its own. POLAR_HEAD = 1 (unit 5, the groups of 4 lanes): the leaf loop ends at p.head_phi and every active path writes the
+// record — no bits; = 2 (unit 6, the list of 32, with that unit's scheduler options): the walk starts at p.head_phi from the
+// record instead of at the resume point of the prefix pass. Every other unit has mode 0 and not one token of this.
+#define POLAR_HEAD (POLAR_ED_TU == 5 ? 1 : 2)
+#define scl_decode_llr_kernel scl_decode_llr_head_kernel
+#define POLAR_KPARAMS PolarHeadParams
 #else
 #define POLAR_KPARAMS PolarDecodeParams
+#endif
+#ifndef POLAR_HEAD
+#define POLAR_HEAD 0
 #endif
 template <int GS, int LDS_LOG, int PIPE, bool ED, int NL = 0, int LAT = 0>
 __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_llr_kernel(POLAR_KPARAMS p) {
@@ -246,6 +267,58 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
         // Pe leaves. The walk resumes at phi = Pe; a layer of size 2S >= Q is read from that buffer
         // (same addresses for every path of the codeword: broadcast) until its first rewrite at phi = 2S.
         int phi_start = 0, forced_top = 0;
+#if POLAR_HEAD == 2
+        {
+            // ---- hand-over from the 4-lane head: lane a of the 4-list is lane a + L - 4 here (the LIFO stack hands out lanes from
+            // the top and no path was killed). The record's rows are copied into this lane's OWN slots; the stack below the
+            // arrivals still holds what the initialisation above wrote. Once per codeword.
+            static_assert(GS == 32 && ED && !LAT && !PIPE && LDS_LOG == 3, "import exists for the list of 32 in its default tuning");
+            const int la = lig - (L - 4);
+            const bool mine = valid && la >= 0 && lig < L;
+            const u64 *rec = p.head_rec + (size_t)(valid ? cw : 0) * (size_t)p.head_rows * 4 + (mine ? la : 0);
+            const u64 st_ = mine ? rec[8] : 0ull;
+            active = (st_ >> 63) != 0;
+            actw = __ballot(active);
+            sp = L - __popcll((actw >> gbase) & gmask);
+            if (active) {
+                pm = __longlong_as_double((long long)rec[0]);
+                clsmall = rec[4];
+                hword = (uint32_t)st_;
+                int r = 3;
+                for (int s = 6; s < n; ++s) {
+                    if (!((p.head_c_mask >> s) & 1u)) continue;
+                    const int nwd = (1 << s) / 32;
+                    uint32_t *dst = g_cl + (size_t)(nwd - 2) * 64 + lane;
+#pragma unroll 1
+                    for (int w = 0; w < nwd; w += 2) {
+                        const u64 x0 = rec[(size_t)(r + w) * 4], x1 = rec[(size_t)(r + w + 1) * 4];
+                        dst[(size_t)w * 64] = (uint32_t)x0; dst[(size_t)(w + 1) * 64] = (uint32_t)x1;
+                    }
+                    pC.set(s, lig);
+                    r += nwd;
+                }
+                for (int s = 5; s < n; ++s) {
+                    if (!((p.head_llr_mask >> s) & 1u)) continue;
+                    const int T = 1 << s;
+                    double *dst = g_llr + (size_t)(T - 2 * SL) * 64 + lane;
+                    // (four rows in flight; more, and the allocator pays for them with spills in the visits)
+#pragma unroll 1
+                    for (int j = 0; j < T; j += 4) {
+                        u64 x[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) x[k] = rec[(size_t)(r + j + k) * 4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) dst[(size_t)(j + k) * 64] = __longlong_as_double((long long)x[k]);
+                    }
+                    pL.set(s, lig);
+                    r += T;
+                }
+            }
+            t = (unsigned)p.head_t;
+            wave_mem_fence();
+            phi_start = p.head_phi;
+        }
+#else
         const double *pre_cw = nullptr;
         if (!LAT && p.prefix_q > 0) {               // (the LAT form is launched without a prefix pass: its walk starts at leaf 0)
             const int Q = p.prefix_q, Pe = p.prefix_len;
@@ -263,8 +336,10 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
             phi_start = Pe;
             if (Pe < Q) forced_top = n - __builtin_ctz((unsigned)Q) + 1;     // recompute from the block downwards
         }
+#endif
 
         PROF_DECL
+        PROF_HEAD_DECL
 #ifdef POLAR_MARGIN
         // development aid (tools/margin_profile.py): the smallest gap, over all pruning fork steps of this codeword, between
         // the worst surviving and the best discarded fork metric — what a lower-precision state would have to resolve
@@ -295,7 +370,12 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
             ctlv_n = ctl_window((phi_start & ~63) + 64);
             ctl_next = (uint32_t)__builtin_amdgcn_readlane((int)ctlv, phi_start & 63);
         } else ctl_next = ctlp[phi_start];
+#if POLAR_HEAD == 1
+        for (int phi = phi_start; phi < p.head_phi; ++phi) {
+#else
         for (int phi = phi_start; phi < N; ++phi) {
+#endif
+            PROF_HEAD(phi)
             PROF(0)
             const uint32_t ctl = ctl_next;
             // recursivelyUpdateC (PolarCode.cpp:457-473) from the layer of size S upwards: X = column 1 of
@@ -394,9 +474,54 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
 #include "polar_scl_visits.inc"
 #include "polar_scl_leaf.inc"
         }  // phi
+        PROF_HEAD_END
         PROF_OUT
 
+#if POLAR_HEAD == 1
+        {
+            // ---- hand-over record (polar_head_plan.h): rows of four words, word `lig` of a row is this path's. The slot pointers are
+            // dereferenced — the record owns its rows —; no bits are written. The codeword's guard flag joins what the prefix pass set.
+            static_assert(GS == 4 && ED && !LAT && !PIPE && LDS_LOG == 3, "export exists for the groups of 4 lanes in the default tuning");
+            (void)K; (void)g_tb;
+            if (valid) {
+                u64 *rec = p.head_rec + (size_t)cw * (size_t)p.head_rows * 4 + lig;
+                rec[0] = active ? (u64)__double_as_longlong(pm) : 0ull;
+                rec[4] = clsmall;
+                rec[8] = (u64)hword | ((u64)t << 32) | ((u64)(active ? 1 : 0) << 63);
+                if (active) {
+                    int r = 3;
+                    for (int s = 6; s < n; ++s) {
+                        if (!((p.head_c_mask >> s) & 1u)) continue;
+                        const int nwd = (1 << s) / 32;
+                        const uint32_t *src = g_cl + (size_t)(nwd - 2) * 64 + gbase + pC.get(s);
+                        for (int w = 0; w < nwd; w += 2) {
+                            const uint32_t x0 = src[(size_t)w * 64], x1 = src[(size_t)(w + 1) * 64];
+                            rec[(size_t)(r + w) * 4] = x0; rec[(size_t)(r + w + 1) * 4] = x1;
+                        }
+                        r += nwd;
+                    }
+                    for (int s = 5; s < n; ++s) {
+                        if (!((p.head_llr_mask >> s) & 1u)) continue;
+                        const int T = 1 << s;
+                        const double *src = g_llr + (size_t)(T - 2 * SL) * 64 + gbase + pL.get(s);
+                        for (int j = 0; j < T; j += 8) {
+                            double x[8];
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) x[k] = src[(size_t)(j + k) * 64];
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) rec[(size_t)(r + j + k) * 4] = (u64)__double_as_longlong(x[k]);
+                        }
+                        r += T;
+                    }
+                }
+            }
+            guard |= __ballot(gacc <= ED_GACC_FLAG);
+            if (valid && lig == 0 && ((guard >> gbase) & gmask) != 0) p.flags[cw] = 1;
+            wave_mem_fence();
+        }
+#else
 #include "polar_scl_finish.inc"
+#endif
         // next group
         if (p.work) {
             unsigned nxt = 0;
@@ -625,12 +750,13 @@ __global__ __launch_bounds__(256) void prefix_kernel(PolarDecodeParams p, int st
     }
 }
 
-// This file is compiled five times (polar_amd/build.py): POLAR_ED_TU = 0 instantiates the LLR-domain kernels and
+// This file is compiled seven times (polar_amd/build.py): POLAR_ED_TU = 0 instantiates the LLR-domain kernels and
 // the small helper kernels, POLAR_ED_TU = 1 the exp-domain kernels of the groups of 4, 8, 16 and 64 lanes, POLAR_ED_TU = 2 the
 // exp-domain list of 32 — translation units that build in parallel, that one with its own scheduler options
 // (max-memory-clause strategy + the AMDGPU register-pressure trackers: +2.2 ... 3.8 % on the headline kernel, -11 % on the
 // groups of 8: build.py) —, POLAR_ED_TU = 3 the exp-domain one-codeword-per-wave (LAT) kernels, POLAR_ED_TU = 4 the
-// LLR-domain batch kernels with the list-output finish (every group size, default tuning only: DESIGN.md §8e).
+// LLR-domain batch kernels with the list-output finish (every group size, default tuning only: DESIGN.md §8e), POLAR_ED_TU = 5 and 6
+// the two phases of the two-phase list of 32 (the 4-lane head that exports, the list of 32 that imports: DESIGN.md §3).
 #ifndef POLAR_ED_TU
 #define POLAR_ED_TU 0
 #endif
@@ -799,6 +925,26 @@ hipError_t polar_launch_decode_llr_list(const PolarListParams &p, int gs, int gr
         case 64: return launch_list<64>(p, grid, st);
         default: return hipErrorInvalidValue;
     }
+}
+#elif POLAR_ED_TU == 5
+// phase A of the two-phase list decode: the groups of 4 lanes, list size 4, up to p.head_phi (`grid` counts waves, whole blocks)
+hipError_t polar_launch_decode_head_export(const PolarHeadParams &p, int grid, hipStream_t st) {
+    if (!p.head_rec || p.L != 4 || p.head_phi <= 0 || p.head_phi >= p.N || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((scl_decode_llr_kernel<4, 3, 0, true>), dim3(grid / 4), dim3(256), polar_decode_lds_bytes(3, 0), st, p);
+    return hipGetLastError();
+}
+#elif POLAR_ED_TU == 6
+// phase B: the list of 32 from p.head_phi on (the instantiations launch_gs<32, true> picks in the default tuning)
+hipError_t polar_launch_decode_head_import(const PolarHeadParams &p, int grid, hipStream_t st) {
+    if (!p.head_rec || p.L < 17 || p.L > 32 || p.head_phi <= 0 || p.head_phi >= p.N || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
+    const size_t lds = polar_decode_lds_bytes(3, 0);
+#ifndef POLAR_NO_FIXED_N
+    if (p.n == 11) hipLaunchKernelGGL((scl_decode_llr_kernel<32, 3, 0, true, 11>), dim3(grid / 4), dim3(256), lds, st, p);
+    else if (p.n == 10) hipLaunchKernelGGL((scl_decode_llr_kernel<32, 3, 0, true, 10>), dim3(grid / 4), dim3(256), lds, st, p);
+    else
+#endif
+    hipLaunchKernelGGL((scl_decode_llr_kernel<32, 3, 0, true>), dim3(grid / 4), dim3(256), lds, st, p);
+    return hipGetLastError();
 }
 #elif POLAR_ED_TU == 2
 hipError_t polar_launch_decode_llr_ed1_gs32(const PolarDecodeParams &p, int lds_log, int pipe, int grid, hipStream_t st) {

@@ -256,7 +256,14 @@
                         // (measured and dropped: not storing layer 1's second half — the largest array — and re-deriving it
                         // from the channel values at its only later reader, the g-visit of layer 2 at phi = 3N/4: -9 % HBM
                         // bytes, but -1.7 % throughput; the re-derivation pass itself is slower than the traffic it saves)
+#if POLAR_HEAD == 2
+                        // (a walk that starts INSIDE the second quarter has no table of the h values — the head kept layer 2 as an
+                        // ordinary layer, handed over in the record — and takes the tables up with the build at N/2; a walk that
+                        // starts AT N/4 runs that build itself, like one that starts before it)
+                        const bool tsrc = tbl && lam == 3 && phi >= S2 && (phi >= S1 || p.head_phi <= S2);
+#else
                         const bool tsrc = tbl && lam == 3 && phi >= S2;       // inputs come from the layer-2 table
+#endif
                         // GMM: bit k set = o_k is HBM-resident and passed as the UNIFORM base of its rows (the lane offset is added as a
                         // 32-bit register offset: global_load/store with an SGPR base, no 64-bit VALU add per access)
                         auto fused4 = [&](const double *inp, double *o0, double *o1, double *o2, double *o3, auto NTT, auto TSS, auto GMM) {

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-phase cycle breakdown of scl_decode_llr_kernel (instrumented build, -DPOLAR_PROFILE).
-Run on the GPU box: python tools/phase_profile.py [L] [batch] [wpc] [lds_log]"""
+Run on the GPU box: python tools/phase_profile.py [L] [batch] [wpc] [lds_log]
+HEAD_PHI=<leaf> (default 432, the headline code's hand-over leaf; 0 = off) also prints the share of the leaf loop's cycles spent
+before that leaf: the few-path head of DESIGN.md §4."""
 import ctypes as C
 import os
 import sys
@@ -9,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from polar_amd import build
-lib = build.build(profile=True)
+lib = os.environ.get("POLAR_PROF_LIB") or build.build(profile=True)      # (an instrumented library built elsewhere)
 import polar_amd
 polar_amd.LIB_PATH = lib
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -26,6 +28,8 @@ g.synth_llr_dev(1, 0, B, g.snr_sqrt_linear(float(os.environ.get("EBNO", "2.0")))
 g.decode_scl_llr_dev(llr.data_ptr(), B, L, out.data_ptr(), prof.data_ptr())
 torch.cuda.synchronize()
 prof.zero_()
+head_phi = int(os.environ.get("HEAD_PHI", "432"))
+prof[32] = head_phi                                       # (read by the kernel: PROF_HEAD_DECL)
 torch.cuda.synchronize()
 import time
 t = time.perf_counter()
@@ -35,16 +39,18 @@ dt = time.perf_counter() - t
 a = prof[:24].cpu().numpy().astype(float)
 names = ["loop ovh", "layer S>SL g (HBM)", "layer S>SL f (HBM)", "layer 4<=S<=SL (LDS)", "layer S<4", "leaf frozen / rate-0 block", "leaf unfrozen (rest: flush etc.)", "partial sums", "unf: DPP reductions+decision", "unf: competitive-bad loop", "unf: stack/srcof", "unf: clone shuffles+update", "-", "unf: setup+goods rank loop", "unf: wait for leaf (ballot)", "unf: softplus+bounds"]
 print(f"L={L} B={B} time {dt*1e3:.2f} ms -> {B/dt:.0f} cw/s")
-cyc = a[:8].sum() + a[16:24].sum()
+cyc = a[:8].sum() + a[16:22].sum()                        # ([22], [23]: the head split below, not phases)
 nwd = B / (64 // max(1, 1 << (L - 1).bit_length()))      # wave-decodes
 if os.environ.get("LATPROF"):                             # the one-codeword-per-wave kernels: a wave-decode is a codeword
     nwd = B
 print(f"  cycles per wave-decode: {cyc/nwd:.0f}")
+if head_phi and a[23] > 0:
+    print(f"  leaves before {head_phi} (few-path head): {100*a[22]/a[23]:.2f}% of the leaf loop  {a[22]/nwd:10.0f} of {a[23]/nwd:.0f} cycles/wave-decode")
 for nm, v in zip(names[:8], a[:8]):
     print(f"  {nm:34s} {100*v/cyc:5.1f}%  {v/nwd:10.0f} cycles/wave-decode")
 sub = ["unf: leaf wait + softplus + DPP bounds", "unf: fast path commit", "unf: goods rank loop", "unf: competitive-bad loop",
        "unf: kill/clone LIFO (LDS)", "unf: clone shuffles + update", "-", "-"]
-for nm, v in zip(sub, a[16:24]):
+for nm, v in zip(sub, a[16:22]):
     if v:
         print(f"    {nm:40s} {100*v/cyc:5.1f}%  {v/nwd:10.0f}")
 if a[8] > 0:
