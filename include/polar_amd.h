@@ -172,6 +172,45 @@ int polar_decode_scl_llr_list_batch(polar_code_t *h, const void *llr, int fmt, l
 int polar_list_find_dev(polar_code_t *h, const uint8_t *d_cand, const int32_t *d_n_active, const uint8_t *d_info, long B, int L,
                         int32_t *d_rank, void *stream);
 
+/* ---- error analysis of the list decoder: the metric of a given word, list-miss / undetected / ML-bound counters ----
+ * polar_path_metric_batch[_dev]: SC along GIVEN decisions. For row b and word r, pm[b][r] is the metric the list decoder assigns to
+ * the path whose information bits are info[b][r][0..K-1] (reference order, as `out` / `cand`), check bits = the handle's CRC matrix
+ * applied to them, frozen bits 0. The R words of a row share its channel row llr[b]. Arithmetic: the LLR-domain list kernel's,
+ * the N leaf terms added in decoding order in one fp64 chain — where the list output of the same row holds that word with
+ * crc_ok = 1, pm equals the list's pm[b][row] BIT FOR BIT (a row with crc_ok = 0 decided other check bits: another path). A word
+ * need not be in any list: the sent word's metric when the decoder lost it is what the ML bound below is made of.
+ * `fmt` = POLAR_LLR_*, alignment rules of the list call; 1 <= R <= POLAR_MAX_LIST (the cand of a list call can be passed back with
+ * R = L). POLAR_E_ARG before the device is touched: NULL pointers, unknown fmt, 16-bit rows at an odd address, R out of range,
+ * negative B; B = 0 is POLAR_OK. _dev: device pointers, stream-ordered, no host synchronisation, one launch (one wave per word, its
+ * N doubles in LDS up to N = 16384, beyond that in handle scratch grown on demand — polar_reserve does not cover it). Host form:
+ * copies in, the launch, a wait, the copy out. */
+int polar_path_metric_batch_dev(polar_code_t *h, const void *d_llr, int fmt, const uint8_t *d_info /*[B][R][K]*/, long B, int R,
+                                double *d_pm /*[B][R]*/, void *stream);
+int polar_path_metric_batch(polar_code_t *h, const void *llr, int fmt, const uint8_t *info, long B, int R, double *pm);
+/* polar_mc_batch_list: like polar_mc_batch / polar_mc_batch_bicm for the trials {t0 + i*stride : i < T}, with the list decoder's end
+ * state classified on the device. Every ENABLED (L, point) simulates all T trials (no "decoded at a lower Eb/N0 => not simulated":
+ * the statistics are per point) and ADDS to stats[(li*n_e + ie)*POLAR_LS_N + c] (host uint64), c =
+ *   POLAR_LS_RUN    every trial
+ *   POLAR_LS_ERR    cand[winner] differs from the sent info (K zeros for winner -1): decode_scl_llr's block error
+ *   POLAR_LS_MISS   no row r < n_active holds the sent info (polar_list_find_dev would return L): even a genie selector fails.
+ *                   MISS <= ERR; ERR - MISS are the selection errors
+ *   POLAR_LS_UNDET  ERR, winner >= 0 and crc_ok[winner] = 1: a wrong word delivered as valid (crc == 0: every error with a winner)
+ *   POLAR_LS_ML     UNDET and pm[winner] <= the sent word's own metric (polar_path_metric_batch_dev): a valid word at least as
+ *                   likely as the sent one exists, so an ML decoder of the concatenated code errs too — the lower bound on ML BLER
+ * `constellation` 0 (or POLAR_CONST_BPSK): BPSK on the Eb/N0 axis; POLAR_CONST_ASK*: the BICM front end on the SNR axis. POLAR_RX_MLC,
+ * NULL pointers, a list size out of range, negative T, stride < 1: POLAR_E_ARG before the device is touched; T = 0 is POLAR_OK and
+ * leaves stats alone. The trials run in chunks (256 MiB of list output, or the "list_chunk_cw" knob), so T is not bounded by the
+ * L K bytes per trial; the counters are read once, at the end of the call. */
+#define POLAR_LS_RUN   0
+#define POLAR_LS_ERR   1
+#define POLAR_LS_MISS  2
+#define POLAR_LS_UNDET 3
+#define POLAR_LS_ML    4
+#define POLAR_LS_N     5
+int polar_mc_batch_list(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride,
+                        const double *axis, int n_e, const uint8_t *L, int n_L, const uint8_t *enabled /*[n_L*n_e]*/,
+                        uint64_t *stats /*[n_L*n_e][POLAR_LS_N]*/);
+
 /* ---- PolarCode::decode_scl_p1 (PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);

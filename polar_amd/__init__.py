@@ -36,6 +36,7 @@ RECEIVERS = ("bicm", "mlc")
 
 LLR_F64, LLR_F32, LLR_F16, LLR_BF16 = 0, 1, 2, 3     # include/polar_amd.h POLAR_LLR_*
 LLR_FORMATS = {"f64": LLR_F64, "f32": LLR_F32, "f16": LLR_F16, "bf16": LLR_BF16}
+LS_RUN, LS_ERR, LS_MISS, LS_UNDET, LS_ML, LS_N = 0, 1, 2, 3, 4, 5     # include/polar_amd.h POLAR_LS_*: columns of the list statistics
 
 
 def _llr_fmt_code(fmt):
@@ -491,6 +492,74 @@ class PolarCode:
         device pointers, asynchronous on `stream`."""
         self._chk(self._L.polar_list_find_dev(self._h, C.c_void_p(cand_ptr), C.c_void_p(n_active_ptr), C.c_void_p(info_ptr),
                                               C.c_long(B), C.c_int(list_size), C.c_void_p(rank_ptr), _stream_ptr(stream)))
+
+    def path_metric(self, llr, info, fmt=None):
+        """The metric the list decoder assigns to given words (polar_path_metric_batch): `llr` [B, N] (or [N]) and `fmt` as
+        decode_scl_llr_list, `info` uint8 [B, K] (one word per row) or [B, R, K] (R <= 64 words per row, sharing the row) ->
+        float64 [B] or [B, R]. Check bits are the CRC matrix's, frozen bits 0. Where decode_scl_llr_list holds the word with
+        crc_ok = 1 the value equals that row's pm bit for bit."""
+        code, a = _llr_rows(llr, fmt)
+        a2 = a.reshape(-1, self.N)
+        B = a2.shape[0]
+        w = np.ascontiguousarray(info, np.uint8)
+        if w.ndim == 1 and B == 1:
+            w = w.reshape(1, -1)
+        if w.ndim not in (2, 3) or w.shape[0] != B or w.shape[-1] != self.K:
+            raise PolarError(f"path_metric: info must be [B, K] or [B, R, K] with B = {B}, K = {self.K}, got shape {w.shape}")
+        R = 1 if w.ndim == 2 else w.shape[1]
+        if not 1 <= R <= 64:
+            raise PolarError("path_metric: %d words per row out of range [1, 64]" % R)
+        pm = np.zeros((B,) if w.ndim == 2 else (B, R), np.float64)
+        self._chk(self._L.polar_path_metric_batch(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_void_p(w.ctypes.data),
+                                                  C.c_long(B), C.c_int(R), C.c_void_p(pm.ctypes.data)))
+        return pm
+
+    def path_metric_dev(self, llr_ptr, fmt, info_ptr, B, R, pm_ptr, stream=None):
+        """Device-resident form (polar_path_metric_batch_dev): LLRs [B, N] of format `fmt`, info uint8 [B, R, K] -> pm float64
+        [B, R]; asynchronous on `stream`."""
+        self._chk(self._L.polar_path_metric_batch_dev(self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_void_p(info_ptr),
+                                                      C.c_long(B), C.c_int(R), C.c_void_p(pm_ptr), _stream_ptr(stream)))
+
+    def mc_batch_list(self, seed, t0, T, stride, axis, list_size_vec, enabled, stats, constellation=0):
+        """polar_mc_batch_list: the trials {t0 + i*stride : i < T} of every enabled (L, point) ADD to stats, uint64
+        [len(L), len(axis), 5] = LS_RUN, LS_ERR, LS_MISS, LS_UNDET, LS_ML. constellation 0: BPSK, `axis` = Eb/N0 in dB; an
+        ASK constellation: the BICM front end, `axis` = SNR in dB."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        enabled = np.ascontiguousarray(enabled, np.uint8)
+        if stats.dtype != np.uint64 or stats.size != len(Ls) * len(ax) * LS_N or not stats.flags.c_contiguous:
+            raise PolarError("stats must be a C-contiguous uint64 array [len(L), len(axis), %d]" % LS_N)
+        if enabled.size != len(Ls) * len(ax):
+            raise PolarError("enabled must have len(L) * len(axis) entries")
+        self._chk(self._L.polar_mc_batch_list(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0),
+                                              C.c_long(T), C.c_long(stride), _p(ax, _dp), C.c_int(len(ax)), _p(Ls, _u8p),
+                                              C.c_int(len(Ls)), _p(enabled, _u8p), _p(stats, _u64p)))
+
+    def list_stats(self, axis, list_size_vec, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0):
+        """Error analysis of the list decoder over a sweep: rounds of mc_batch_list (`batch` trials each; 0: max(256, 2 max_err)
+        first, then doubling up to 262144), a point leaves the sweep once ERR > max_err or RUN >= max_runs (no round takes a point
+        past max_runs). Returns a dict: `stats` uint64 [len(L), len(axis), 5] (LS_* columns), and `bler`, `miss_rate`,
+        `undetected_rate`, `ml_bound` = ERR, MISS, UNDET, ML over RUN, float64 [len(L), len(axis)]."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        if max_runs < 1 or batch < 0:
+            raise PolarError("list_stats: max_runs must be positive and batch non-negative")
+        stats = np.zeros((len(Ls), len(ax), LS_N), np.uint64)
+        done, step = 0, int(batch) if batch else max(256, 2 * int(max_err))
+        while done < max_runs:
+            enabled = ((stats[:, :, LS_ERR] <= max_err) & (stats[:, :, LS_RUN] < max_runs)).astype(np.uint8)
+            if not enabled.any():
+                break
+            T = min(step, max_runs - done)
+            self.mc_batch_list(seed, done, T, 1, ax, Ls, enabled, stats, constellation)
+            done += T
+            if not batch:
+                step = min(2 * step, 262144)
+        run = np.maximum(stats[:, :, LS_RUN], 1).astype(np.float64)
+        res = {"stats": stats}
+        for name, col in (("bler", LS_ERR), ("miss_rate", LS_MISS), ("undetected_rate", LS_UNDET), ("ml_bound", LS_ML)):
+            res[name] = stats[:, :, col] / run
+        return res
 
     def decode_scl_llr_dev_f32(self, llr_ptr, B, list_size, out_ptr, pm_ptr=0, stream=None):
         """Device-resident float32 LLRs [B, N] -> uint8 [B, K]; asynchronous on `stream`."""

@@ -109,6 +109,57 @@ public:
                                               r.n_active.data(), r.winner.data()));
         return r;
     }
+    // The metric the list decoder assigns to given words (polar_path_metric_batch): B codewords back to back, R words of info_length
+    // bits per codeword ([B][R][K]; check bits from the CRC matrix) -> [B][R]. Where decode_scl_llr_list holds a word with
+    // crc_ok = 1 the value is that row's pm bit for bit.
+    std::vector<double> path_metric(const std::vector<double> &llr, const std::vector<uint8_t> &info, int words_per_codeword = 1) {
+        need(llr.size() % _block_length == 0, "path_metric: size must be a multiple of block_length");
+        const long B = (long)(llr.size() / _block_length);
+        need(words_per_codeword >= 1 && words_per_codeword <= POLAR_MAX_LIST, "path_metric: words per codeword out of range");
+        need(info.size() == (size_t)B * words_per_codeword * _info_length, "path_metric: info must hold B * R * info_length bits");
+        std::vector<double> pm((size_t)B * words_per_codeword);
+        check(polar_path_metric_batch(_h, llr.data(), POLAR_LLR_F64, info.data(), B, words_per_codeword, pm.data()));
+        return pm;
+    }
+    // Error analysis of the list decoder over a sweep (polar_mc_batch_list in rounds, as get_bler_quick stops its points: a point
+    // leaves once ERR > max_err or RUN >= max_runs). Rounds of `batch` trials; 0: max(256, 2 max_err), then doubling up to 262144.
+    // Everything is [list_index * n_points + point_index]; stats additionally * POLAR_LS_N + POLAR_LS_*.
+    struct ListStats {
+        int n_L = 0, n_points = 0;
+        std::vector<uint64_t> stats;
+        std::vector<double> bler, miss_rate, undetected_rate, ml_bound;
+    };
+    ListStats list_stats(const std::vector<double> &axis, const std::vector<uint8_t> &list_size, long max_runs = 1000, long max_err = 100,
+                         uint64_t seed = 0, long batch = 0, int constellation = 0) {
+        need(max_runs >= 1 && batch >= 0, "list_stats: max_runs must be positive and batch non-negative");
+        ListStats r;
+        r.n_L = (int)list_size.size(); r.n_points = (int)axis.size();
+        const size_t P = list_size.size() * axis.size();
+        r.stats.assign(P * POLAR_LS_N, 0);
+        std::vector<uint8_t> enabled(P);
+        long done = 0, step = batch ? batch : (2 * max_err > 256 ? 2 * max_err : 256);
+        while (done < max_runs) {
+            bool any = false;
+            for (size_t i = 0; i < P; ++i) {
+                enabled[i] = (long)r.stats[i * POLAR_LS_N + POLAR_LS_ERR] <= max_err && (long)r.stats[i * POLAR_LS_N + POLAR_LS_RUN] < max_runs;
+                any = any || enabled[i];
+            }
+            if (!any) break;
+            const long T = step < max_runs - done ? step : max_runs - done;
+            check(polar_mc_batch_list(_h, constellation, seed, (uint64_t)done, T, 1, axis.data(), r.n_points, list_size.data(), r.n_L,
+                                      enabled.data(), r.stats.data()));
+            done += T;
+            if (!batch) step = 2 * step < 262144 ? 2 * step : 262144;
+        }
+        r.bler.resize(P); r.miss_rate.resize(P); r.undetected_rate.resize(P); r.ml_bound.resize(P);
+        for (size_t i = 0; i < P; ++i) {
+            const uint64_t *s = &r.stats[i * POLAR_LS_N];
+            const double run = s[POLAR_LS_RUN] ? (double)s[POLAR_LS_RUN] : 1.0;
+            r.bler[i] = s[POLAR_LS_ERR] / run; r.miss_rate[i] = s[POLAR_LS_MISS] / run;
+            r.undetected_rate[i] = s[POLAR_LS_UNDET] / run; r.ml_bound[i] = s[POLAR_LS_ML] / run;
+        }
+        return r;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

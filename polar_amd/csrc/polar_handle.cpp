@@ -363,7 +363,7 @@ void polar_destroy(polar_code_t *h) {
     h->d_crc_mask.release(); h->d_tabs.release(); h->d_pre.release(); h->d_llr_scr.release(); h->d_c_scr.release(); h->d_hist_scr.release();
     h->d_in.release(); h->d_f32.release(); h->d_out.release(); h->d_bytes_a.release(); h->d_bytes_b.release();
     h->d_counter.release(); h->d_sel.release(); h->d_work.release();
-    h->d_ech.release(); h->d_flags.release(); h->d_list.release(); h->d_count.release(); h->d_bicm_llr.release(); h->d_list_out.release();
+    h->d_ech.release(); h->d_flags.release(); h->d_list.release(); h->d_count.release(); h->d_bicm_llr.release(); h->d_list_out.release(); h->d_metric_scr.release();
     h->d_alive[0].release(); h->d_alive[1].release(); h->d_nalive.release(); h->d_mc_ctr.release();
     for (auto &sl : h->mc_slots) { sl.list[0].release(); sl.list[1].release(); }
     h->d_slot_n.release();

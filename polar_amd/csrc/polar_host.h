@@ -6,7 +6,8 @@
 //                         decode_impl, the device-resident entry points, P1 paths, encoder
 //   polar_mlc.cpp         MLC receiver: checks, parameter fill, dispatch of the multistage SC kernels, its entry points
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
-//   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev
+//   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev, path metric of given words,
+//                         the list statistics of the sweep (polar_mc_batch_list)
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction
 //   polar_mc_schedule.h   the schedule of the pipelined rounds alone (standard library only: tests/test_mc_schedule.py runs it on a CPU)
@@ -261,6 +262,7 @@ struct polar_code {
     DevBuf<uint32_t> d_list;
     DevBuf<unsigned int> d_count;
     DevBuf<double> d_list_out;       // host-pointer list call: one chunk of list output (metrics, counts, winners, bits, CRC flags: polar_list.cpp)
+    DevBuf<double> d_metric_scr;     // path metric of given words: the per-wave rows [grid][N] of the codes too long for LDS, and the sweep's sent-word metrics (polar_list.cpp)
     DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never
@@ -414,6 +416,8 @@ int bicm_check(int constellation, double n0);             // POLAR_E_ARG for an 
 void fill_demap(int cid, int N, double n0, PolarDemapParams &p);
 // demap B rows of symbols on `st` into the context's own LLR buffer (grown on demand): *d_llr = what decode_impl reads
 int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, long B, hipStream_t st, const double **d_llr);
+// polar_montecarlo.cpp — the channel of a sweep point in synth_kernel's parameters: BPSK at an Eb/N0 (constellation 0) or ASK / BICM at an SNR, both in dB
+void fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point);
 // polar_hostpipe.cpp
 // rows that are received symbols instead of LLRs (polar_decode_bicm_batch*): M elements per row, demapped on the device
 struct SymRows { int cid, M; double n0; };

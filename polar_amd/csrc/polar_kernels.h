@@ -183,6 +183,26 @@ hipError_t polar_launch_list_find(const uint8_t *cand, const int32_t *n_active, 
                                   int32_t *rank_out, hipStream_t st);
 hipError_t polar_launch_count_errors(const uint8_t *a, const uint8_t *b, long B, int K,
                                      unsigned long long *err, uint8_t *mismatch_flags, hipStream_t st);
+// Path metric of given words (polar_kernels_metric.hip; include/polar_amd.h polar_path_metric_batch_dev): one wave per (row, word)
+struct PolarMetricParams {
+    int n, N, K, crc, R;
+    long B;
+    const void *llr;             // [B][N] device, elements of llr_fmt (POLAR_LLR_*)
+    int llr_fmt;
+    const uint8_t *info;         // [B][R][K] device
+    const uint16_t *order;       // [N] device
+    const uint8_t *crcm;         // [crc][K] device
+    const double *tabs;          // [322] device
+    double *scr;                 // nullptr: the N doubles of a word in LDS (polar_metric_lds_bytes(n, 1) must fit); else [grid][N] device
+    double *pm;                  // [B][R] device
+};
+size_t polar_metric_lds_bytes(int n, int in_lds);
+hipError_t polar_launch_path_metric(const PolarMetricParams &p, int grid, hipStream_t st);
+// The five counters of the list statistics (include/polar_amd.h POLAR_LS_*, polar_kernels_metric.hip): rows [0, min(B, *n_dev)) of a list
+// output against the sent info [B][K] and the sent word's own metric pm_sent [B]; ctr[0..4] are ADDED to
+hipError_t polar_launch_list_classify(const uint8_t *cand, const double *pm, const uint8_t *crc_ok, const int32_t *n_active,
+                                      const int32_t *winner, const uint8_t *sent, const double *pm_sent, long B, int L, int K,
+                                      const unsigned int *n_dev, unsigned long long *ctr, hipStream_t st);
 // Monte-Carlo round on the device (PolarCode.cpp:728-742, 758-769): alive[i] = t0 + i*stride, *n = T
 hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T, hipStream_t st);
 // rows [0, min(B, *n_in)): block error iff decoded != sent; ctr[0] += block errors, ctr[1] += differing bits

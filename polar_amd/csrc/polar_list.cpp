@@ -34,6 +34,31 @@ int list_launch(polar_code *h, const void *d_llr, int fmt, long B, int L, uint8_
     return POLAR_OK;
 }
 
+// ---- path metric of given words (polar_kernels_metric.hip) ----
+int metric_check(const polar_code *h, const void *llr, int fmt, const uint8_t *info, long B, int R, const double *pm) {
+    return check_args(h && llr && info && pm, R, B, [&] { return llr_fmt_check(fmt, llr); });
+}
+
+// (arguments checked, B > 0, the handle's device current) One wave per word; its N doubles in LDS while they fit, else in a row of
+// the handle's scratch per resident wave
+int metric_launch(polar_code *h, const void *d_llr, int fmt, const uint8_t *d_info, long B, int R, double *d_pm, hipStream_t st) {
+    PolarMetricParams p;
+    p.n = h->n; p.N = h->N; p.K = h->K; p.crc = h->crc; p.R = R; p.B = B;
+    p.llr = d_llr; p.llr_fmt = fmt; p.info = d_info; p.order = h->d_order.p; p.crcm = h->d_crcm.p; p.tabs = h->d_tabs.p;
+    p.scr = nullptr; p.pm = d_pm;
+    const long words = B * (long)R;
+    long grid = std::min<long>(words, 8192);
+    if (polar_metric_lds_bytes(h->n, 1) > h->lds_per_block) {
+        if (polar_metric_lds_bytes(h->n, 0) > h->lds_per_block) return fail(POLAR_E_UNSUPPORTED, "the path-metric kernel's LDS does not fit this device");
+        grid = std::min<long>(grid, (long)h->num_cu * 2);
+        int rc;
+        if ((rc = h->d_metric_scr.ensure((size_t)grid * h->N))) return rc;
+        p.scr = h->d_metric_scr.p;
+    }
+    HIP_TRY(polar_launch_path_metric(p, (int)grid, st));
+    return POLAR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -86,6 +111,98 @@ int polar_list_find_dev(polar_code_t *h, const uint8_t *d_cand, const int32_t *d
     DevGuard dg_;
     if ((rc = ensure_device(h, dg_))) return rc;
     HIP_TRY(polar_launch_list_find(d_cand, d_n_active, d_info, B, L, h->K, d_rank, (hipStream_t)stream));
+    return POLAR_OK;
+}
+
+int polar_path_metric_batch_dev(polar_code_t *h, const void *d_llr, int fmt, const uint8_t *d_info, long B, int R, double *d_pm, void *stream) {
+    int rc = metric_check(h, d_llr, fmt, d_info, B, R, d_pm);
+    if (rc || B == 0) return rc;
+    DevGuard dg_;
+    if ((rc = ensure_device(h, dg_))) return rc;
+    return metric_launch(h, d_llr, fmt, d_info, B, R, d_pm, (hipStream_t)stream);
+}
+
+int polar_path_metric_batch(polar_code_t *h, const void *llr, int fmt, const uint8_t *info, long B, int R, double *pm) {
+    int rc = metric_check(h, llr, fmt, info, B, R, pm);
+    if (rc || B == 0) return rc;
+    DevGuard dg_;
+    if ((rc = ensure_device(h, dg_))) return rc;
+    const size_t row = (size_t)h->N * polar_llr_esz(fmt), words = (size_t)B * R;
+    if ((rc = h->d_in.ensure(((size_t)B * row + 7) / 8))) return rc;
+    if ((rc = h->d_bytes_b.ensure(words * h->K))) return rc;
+    if ((rc = h->d_list_out.ensure(words))) return rc;
+    HIP_TRY(hipMemcpy(h->d_in.p, llr, (size_t)B * row, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_bytes_b.p, info, words * h->K, hipMemcpyHostToDevice));
+    if ((rc = metric_launch(h, h->d_in.p, fmt, h->d_bytes_b.p, B, R, h->d_list_out.p, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(pm, h->d_list_out.p, words * sizeof(double), hipMemcpyDeviceToHost));
+    return POLAR_OK;
+}
+
+// Per enabled (list size, point) and per chunk of trials, stream-ordered: the trials' LLRs and sent info (synth_kernel), the list
+// decode, the sent word's own metric (one word per row), the classification. The counters stay on the device until the end.
+int polar_mc_batch_list(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis, int n_e,
+                        const uint8_t *L, int n_L, const uint8_t *enabled, uint64_t *stats) {
+    if (!h || !axis || !L || !enabled || !stats) return fail(POLAR_E_ARG, "NULL argument");
+    if (constellation & POLAR_RX_MLC) return fail(POLAR_E_ARG, "the list statistics have no MLC receiver");
+    if (constellation != 0 && !is_ask_constellation(constellation)) return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
+    if (T < 0 || stride <= 0 || n_e <= 0 || n_L <= 0) return fail(POLAR_E_ARG, "bad sizes");
+    for (int i = 0; i < n_L; ++i)
+        if (L[i] < 1 || L[i] > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range", (int)L[i]);
+    if (T == 0) return POLAR_OK;
+    const int cid = constellation == POLAR_CONST_BPSK ? 0 : constellation;       // (BPSK on the Eb/N0 axis under either name)
+    DevGuard dg_;
+    int rc = ensure_device(h, dg_);
+    if (rc) return rc;
+    const int N = h->N, K = h->K, P = n_e * n_L;
+    int Lmax = 1;
+    for (int i = 0; i < n_L; ++i) Lmax = std::max<int>(Lmax, L[i]);
+    auto chunk_of = [&](int Ls) {
+        const size_t per = (size_t)Ls * K + 9 * (size_t)Ls + 8;
+        return std::min<long>(T, h->knobs.list_chunk_cw > 0 ? h->knobs.list_chunk_cw : std::max<long>(1, (long)(((size_t)256 << 20) / per)));
+    };
+    long cmax = 0; size_t out_max = 0;
+    for (int i = 0; i < n_L; ++i) {
+        const long c = chunk_of(L[i]);
+        cmax = std::max(cmax, c);
+        out_max = std::max(out_max, (size_t)c * ((size_t)L[i] * K + 9 * (size_t)L[i] + 8));
+    }
+    // (every buffer at its largest before the first launch: a DevBuf that grows frees what work in flight may still read)
+    if ((rc = h->d_in.ensure((size_t)cmax * N))) return rc;
+    if ((rc = h->d_bytes_a.ensure((size_t)cmax * K))) return rc;                 // sent info
+    if ((rc = h->d_list_out.ensure((out_max + 7) / 8 + 1 + (size_t)cmax))) return rc;
+    if ((rc = h->d_mc_ctr.ensure((size_t)POLAR_LS_N * P))) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_mc_ctr.p, 0, (size_t)POLAR_LS_N * P * sizeof(unsigned long long), nullptr));
+    for (int li = 0; li < n_L; ++li) {
+        const int Ls = L[li];
+        const long chunk = chunk_of(Ls);
+        const size_t LK = (size_t)Ls * K;
+        // one chunk of list output: metrics first, the sent words' metrics, the two int32 arrays, then the bytes
+        double *d_pm = h->d_list_out.p, *d_pms = d_pm + (size_t)chunk * Ls;
+        int32_t *d_na = reinterpret_cast<int32_t *>(d_pms + chunk), *d_win = d_na + chunk;
+        uint8_t *d_cand = reinterpret_cast<uint8_t *>(d_win + chunk), *d_crc = d_cand + (size_t)chunk * LK;
+        for (int ie = 0; ie < n_e; ++ie) {
+            if (!enabled[li * n_e + ie]) continue;
+            for (long c0 = 0; c0 < T; c0 += chunk) {
+                const long c = std::min(chunk, T - c0);
+                PolarEncodeParams p;
+                fill_enc(h, p);
+                p.B = c; p.seed = seed; p.trial0 = t0 + (uint64_t)c0 * (uint64_t)stride; p.stride = stride;
+                fill_channel(h, p, cid, axis[ie]);
+                p.llr = h->d_in.p; p.info_out = h->d_bytes_a.p;
+                HIP_TRY(polar_launch_synth(p, nullptr));
+                if ((rc = list_launch(h, h->d_in.p, POLAR_LLR_F64, c, Ls, d_cand, d_pm, d_crc, d_na, d_win, nullptr))) return rc;
+                if ((rc = metric_launch(h, h->d_in.p, POLAR_LLR_F64, h->d_bytes_a.p, c, 1, d_pms, nullptr))) return rc;
+                HIP_TRY(polar_launch_list_classify(d_cand, d_pm, d_crc, d_na, d_win, h->d_bytes_a.p, d_pms, c, Ls, K, nullptr,
+                                                   h->d_mc_ctr.p + (size_t)POLAR_LS_N * (li * n_e + ie), nullptr));
+            }
+        }
+    }
+    std::vector<unsigned long long> ctr((size_t)POLAR_LS_N * P);
+    HIP_TRY(hipMemcpy(ctr.data(), h->d_mc_ctr.p, ctr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int i = 0; i < P; ++i)
+        if (enabled[i])
+            for (int k = 0; k < POLAR_LS_N; ++k) stats[(size_t)i * POLAR_LS_N + k] += (uint64_t)ctr[(size_t)i * POLAR_LS_N + k];
     return POLAR_OK;
 }
 

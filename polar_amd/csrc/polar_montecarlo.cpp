@@ -5,10 +5,8 @@
 #include "polar_mc_schedule.h"
 #include "polar_multi.h"
 
-extern "C" {
-
 // ---- Monte-Carlo (PolarCode::get_bler_quick, PolarCode.cpp:658-785) -----------------------
-static void fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point) {
+void polar_host::fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point) {
     p.constellation = constellation;
     if (constellation == 0) {
         p.s = polar_snr_sqrt_linear(h, snr_point);           // Eb/N0 in dB, PolarCode.cpp:744-745
@@ -21,6 +19,8 @@ static void fill_channel(const polar_code *h, PolarEncodeParams &p, int constell
         p.info_block_div = 1;                                // fresh info every run (:50)
     }
 }
+
+extern "C" {
 
 // One Monte-Carlo round of T trials {t0 + i*stride} for every enabled (L, Eb/N0) point, entirely stream-ordered on
 // the device: per list size the alive list starts with all T trials; per point: synth(alive) -> decode -> count
