@@ -211,6 +211,53 @@ int polar_mc_batch_list(polar_code_t *h, int constellation, uint64_t seed, uint6
                         const double *axis, int n_e, const uint8_t *L, int n_L, const uint8_t *enabled /*[n_L*n_e]*/,
                         uint64_t *stats /*[n_L*n_e][POLAR_LS_N]*/);
 
+/* ---- adaptive list decoding: escalate the list size until the CRC passes (Li, Shen, Tse 2012) ----
+ * (no member of the reference's class.) A schedule is n_s list sizes Ls[0] < Ls[1] < ... < Ls[n_s-1], 1 <= n_s <=
+ * POLAR_AD_MAX_STAGES, each in 1 .. POLAR_MAX_LIST, any value (not only powers of two); a single entry is valid. Stage s decodes a
+ * codeword with a list of Ls[s] and ACCEPTS it when the winner is an active path that itself passes the handle's CRC — in terms of
+ * polar_decode_scl_llr_list_batch_dev at that list size: winner >= 0 && crc_ok[winner] == 1; the winner the reference takes when no
+ * path passes is not accepted. Only codewords not accepted go on to stage s + 1. With s* = the first accepted stage, or n_s - 1:
+ *   out[B][K]   uint8   information bits of the list-of-Ls[s*] decode: bit for bit cand[b][winner[b]] of the list call at that list
+ *                       size, hence polar_decode_scl_llr_batch_fmt(.., Ls[s*]); K zeros for winner -1
+ *   pm[B]       double  that winner's path metric, bit for bit the list call's pm[b][winner] (+inf for winner -1)
+ *   stage[B]    uint8   s*
+ *   crc_ok[B]   uint8   1 = stage s* accepted the word; 0 only at the last stage (always 0 for winner -1)
+ * out / d_out is required, the other three outputs may be NULL. Arithmetic as the list call's: the LLR-domain batch kernel (mode 1's,
+ * the reference's bits) at its default tuning; polar_set_mode, polar_set_tuning and the latency threshold do not affect it. A handle
+ * with crc == 0 is refused (POLAR_E_ARG): there is nothing to accept on. POLAR_E_ARG, before the device is touched: NULL handle /
+ * rows / out / schedule, n_s out of range, a size out of range, a schedule that is not strictly increasing, unknown fmt, 16-bit rows
+ * at an odd address, negative B; B = 0 is POLAR_OK.
+ *   _dev   device pointers (the schedule is a host array), stream-ordered on `stream`, no host synchronisation: one memset of a small
+ *          control block, the prefix launch of stage 0 (where the code has an all-frozen prefix and Ls[0] >= 3), n_s decode launches
+ *          and n_s - 1 launches between them that turn the retry flags into the next stage's work list. A later stage's grid is
+ *          sized for B (the host never learns a count); its waves past the end of the list leave at once. Two calls on one handle
+ *          and one stream need no synchronisation between them. It grows the handle's scratch on demand like the other _dev calls;
+ *          polar_reserve's no-allocation promise does NOT cover it.
+ *   host   host pointers: one copy of all B rows in, the _dev sequence, a wait, the copies out. No pipelining, no pinned staging:
+ *          a convenience form like the list call's.
+ * polar_mc_batch_adaptive: like polar_mc_batch_list for ONE schedule: every ENABLED point of `axis` simulates all the trials
+ * {t0 + i*stride : i < T} and ADDS to stats[ie*(3 + n_s) + c] (host uint64), c =
+ *   POLAR_AD_RUN         every trial
+ *   POLAR_AD_ERR         the delivered word differs from the sent info
+ *   POLAR_AD_UNDET       ERR and crc_ok = 1: a wrong word delivered as valid
+ *   POLAR_AD_STAGE0 + s  trials delivered by stage s (they add up to RUN)
+ * `constellation` as polar_mc_batch_list (BPSK on the Eb/N0 axis, POLAR_CONST_ASK*: the BICM front end on the SNR axis; POLAR_RX_MLC,
+ * NULL pointers, a bad schedule, crc == 0, negative T, stride < 1: POLAR_E_ARG before the device is touched; T = 0 is POLAR_OK and
+ * leaves stats alone). The trials run in chunks (512 MiB of LLR rows, or the "list_chunk_cw" knob); the counters are classified on
+ * the device and read once, at the end of the call. */
+#define POLAR_AD_MAX_STAGES 8
+int polar_decode_scl_llr_adaptive_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, const uint8_t *Ls, int n_s,
+                                            uint8_t *d_out, double *d_pm, uint8_t *d_stage, uint8_t *d_crc_ok, void *stream);
+int polar_decode_scl_llr_adaptive_batch(polar_code_t *h, const void *llr, int fmt, long B, const uint8_t *Ls, int n_s,
+                                        uint8_t *out, double *pm, uint8_t *stage, uint8_t *crc_ok);
+#define POLAR_AD_RUN 0      /* every trial */
+#define POLAR_AD_ERR 1      /* delivered word differs from the sent info */
+#define POLAR_AD_UNDET 2    /* ERR and crc_ok = 1 */
+#define POLAR_AD_STAGE0 3   /* + s: trials delivered by stage s */
+int polar_mc_batch_adaptive(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride,
+                            const double *axis, int n_e, const uint8_t *Ls, int n_s, const uint8_t *enabled /*[n_e]*/,
+                            uint64_t *stats /*[n_e][3 + n_s], ADDED to*/);
+
 /* ---- PolarCode::decode_scl_p1 (PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);

@@ -37,6 +37,8 @@ RECEIVERS = ("bicm", "mlc")
 LLR_F64, LLR_F32, LLR_F16, LLR_BF16 = 0, 1, 2, 3     # include/polar_amd.h POLAR_LLR_*
 LLR_FORMATS = {"f64": LLR_F64, "f32": LLR_F32, "f16": LLR_F16, "bf16": LLR_BF16}
 LS_RUN, LS_ERR, LS_MISS, LS_UNDET, LS_ML, LS_N = 0, 1, 2, 3, 4, 5     # include/polar_amd.h POLAR_LS_*: columns of the list statistics
+AD_RUN, AD_ERR, AD_UNDET, AD_STAGE0 = 0, 1, 2, 3     # include/polar_amd.h POLAR_AD_*: columns of the adaptive statistics (+ one per stage)
+AD_MAX_STAGES = 8
 
 
 def _llr_fmt_code(fmt):
@@ -560,6 +562,85 @@ class PolarCode:
         for name, col in (("bler", LS_ERR), ("miss_rate", LS_MISS), ("undetected_rate", LS_UNDET), ("ml_bound", LS_ML)):
             res[name] = stats[:, :, col] / run
         return res
+
+    @staticmethod
+    def _schedule(schedule):
+        """A schedule of list sizes as the uint8 array the C-ABI takes (values out of uint8's range are refused here: the
+        conversion would wrap them)."""
+        v = [int(x) for x in np.atleast_1d(np.asarray(schedule)).tolist()]
+        if any(not 0 <= x <= 255 for x in v):
+            raise PolarError("list size out of range [1, 64] in schedule %r" % (v,))
+        return np.array(v, np.uint8)
+
+    def decode_scl_llr_adaptive(self, llr, schedule=(1, 4, 32), fmt=None):
+        """Adaptive list decoding (polar_decode_scl_llr_adaptive_batch): every row is decoded with the list sizes of `schedule`
+        (strictly increasing, at most 8, each 1 .. 64) in turn until the winner passes the CRC. Returns (out [B, K] uint8, pm [B]
+        float64, stage [B] uint8, crc_ok [B] uint8): the word, its metric, the stage that delivered it and whether that stage
+        accepted it (0 only at the last stage). out equals decode_scl_llr at the list size schedule[stage]. `llr` and `fmt` as
+        decode_scl_llr_list; a single row [N] is a batch of one. The code needs a CRC."""
+        code, a = _llr_rows(llr, fmt)
+        a2 = a.reshape(-1, self.N)
+        B, Ls = a2.shape[0], self._schedule(schedule)
+        out = np.zeros((B, self.K), np.uint8)
+        pm = np.zeros(B, np.float64)
+        stage = np.zeros(B, np.uint8)
+        crc_ok = np.zeros(B, np.uint8)
+        self._chk(self._L.polar_decode_scl_llr_adaptive_batch(
+            self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), _p(Ls, _u8p), C.c_int(len(Ls)), _p(out, _u8p),
+            C.c_void_p(pm.ctypes.data), C.c_void_p(stage.ctypes.data), C.c_void_p(crc_ok.ctypes.data)))
+        return out, pm, stage, crc_ok
+
+    def decode_scl_llr_adaptive_dev(self, llr_ptr, fmt, B, schedule, out_ptr, pm_ptr=0, stage_ptr=0, crc_ok_ptr=0, stream=None):
+        """Device-resident form (polar_decode_scl_llr_adaptive_batch_dev): LLRs [B, N] of format `fmt` -> out uint8 [B, K] and,
+        where a pointer is given, pm float64 [B], stage uint8 [B], crc_ok uint8 [B]; asynchronous on `stream`, no host
+        synchronisation between the stages."""
+        Ls = self._schedule(schedule)
+        self._chk(self._L.polar_decode_scl_llr_adaptive_batch_dev(
+            self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B), _p(Ls, _u8p), C.c_int(len(Ls)),
+            C.c_void_p(out_ptr), C.c_void_p(pm_ptr), C.c_void_p(stage_ptr), C.c_void_p(crc_ok_ptr), _stream_ptr(stream)))
+
+    def mc_batch_adaptive(self, seed, t0, T, stride, axis, schedule, enabled, stats, constellation=0):
+        """polar_mc_batch_adaptive: the trials {t0 + i*stride : i < T} of every enabled point ADD to stats, uint64
+        [len(axis), 3 + len(schedule)] = AD_RUN, AD_ERR, AD_UNDET, then the trials delivered by each stage. constellation 0: BPSK,
+        `axis` = Eb/N0 in dB; an ASK constellation: the BICM front end, `axis` = SNR in dB."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        Ls = self._schedule(schedule)
+        enabled = np.ascontiguousarray(enabled, np.uint8)
+        cols = AD_STAGE0 + len(Ls)
+        if stats.dtype != np.uint64 or stats.size != len(ax) * cols or not stats.flags.c_contiguous:
+            raise PolarError("stats must be a C-contiguous uint64 array [len(axis), %d]" % cols)
+        if enabled.size != len(ax):
+            raise PolarError("enabled must have len(axis) entries")
+        self._chk(self._L.polar_mc_batch_adaptive(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0),
+                                                  C.c_long(T), C.c_long(stride), _p(ax, _dp), C.c_int(len(ax)), _p(Ls, _u8p),
+                                                  C.c_int(len(Ls)), _p(enabled, _u8p), _p(stats, _u64p)))
+
+    def adaptive_stats(self, axis, schedule, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0):
+        """The adaptive decoder over a sweep: rounds of mc_batch_adaptive like list_stats' (`batch` trials each; 0: max(256,
+        2 max_err) first, then doubling up to 262144), a point leaves the sweep once ERR > max_err or RUN >= max_runs. Returns a
+        dict: `stats` uint64 [len(axis), 3 + len(schedule)] (AD_* columns), `bler` and `undetected_rate` = ERR and UNDET over RUN
+        [len(axis)], `stage_share` [len(axis), len(schedule)] = the share of the trials each stage delivered, and `mean_effort`
+        [len(axis)] = the mean over the trials of schedule[0] + ... + schedule[stage]: the list sizes a codeword went through
+        (a fixed list of L costs L)."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        Ls = self._schedule(schedule)
+        if max_runs < 1 or batch < 0:
+            raise PolarError("adaptive_stats: max_runs must be positive and batch non-negative")
+        stats = np.zeros((len(ax), AD_STAGE0 + len(Ls)), np.uint64)
+        done, step = 0, int(batch) if batch else max(256, 2 * int(max_err))
+        while done < max_runs:
+            enabled = ((stats[:, AD_ERR] <= max_err) & (stats[:, AD_RUN] < max_runs)).astype(np.uint8)
+            if not enabled.any():
+                break
+            T = min(step, max_runs - done)
+            self.mc_batch_adaptive(seed, done, T, 1, ax, Ls, enabled, stats, constellation)
+            done += T
+            if not batch:
+                step = min(2 * step, 262144)
+        run = np.maximum(stats[:, AD_RUN], 1).astype(np.float64)
+        share = stats[:, AD_STAGE0:] / run[:, None]
+        return {"stats": stats, "bler": stats[:, AD_ERR] / run, "undetected_rate": stats[:, AD_UNDET] / run, "stage_share": share,
+                "mean_effort": share @ np.cumsum(Ls.astype(np.float64))}
 
     def decode_scl_llr_dev_f32(self, llr_ptr, B, list_size, out_ptr, pm_ptr=0, stream=None):
         """Device-resident float32 LLRs [B, N] -> uint8 [B, K]; asynchronous on `stream`."""

@@ -17,10 +17,11 @@ CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libpolar_amd.so")
 BUILD = os.path.join(HERE, "_build")
-# (source, extra -D, object tag, extra compiler options): polar_kernels.hip is compiled seven times — LLR-domain kernel family,
+# (source, extra -D, object tag, extra compiler options): polar_kernels.hip is compiled eight times — LLR-domain kernel family,
 # exp-domain kernels of the small groups, exp-domain list of 32 (the headline kernel, with its own scheduler options), exp-domain
 # one-codeword-per-wave kernels, LLR-domain kernels with the list-output finish (decode_scl_llr_list), the two phases of the
-# two-phase list of 32 (the 4-lane head that exports, the list of 32 that imports: the scheduler options of the list of 32)
+# two-phase list of 32 (the 4-lane head that exports, the list of 32 that imports: the scheduler options of the list of 32),
+# LLR-domain kernels with the adaptive finish (decode_scl_llr_adaptive)
 FLAGS_LIST32 = ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause", "-mllvm", "-amdgpu-use-amdgpu-trackers"] + \
                os.environ.get("POLAR_LIST32_FLAGS", "").split()          # (A/B experiments on the list-of-32 translation unit alone)
 # the one-codeword-per-wave kernels (a lone wave: every instruction is 4 cycles, a taken branch 20 — DESIGN.md §7)
@@ -29,11 +30,12 @@ SOURCES = [("polar_kernels.hip", ["POLAR_ED_TU=0"], "", []), ("polar_kernels.hip
            ("polar_kernels.hip", ["POLAR_ED_TU=2"], ".ed32", FLAGS_LIST32), ("polar_kernels.hip", ["POLAR_ED_TU=3"], ".lat", FLAGS_LAT),
            ("polar_kernels.hip", ["POLAR_ED_TU=4"], ".list", []),
            ("polar_kernels.hip", ["POLAR_ED_TU=5"], ".headA", []), ("polar_kernels.hip", ["POLAR_ED_TU=6"], ".headB", FLAGS_LIST32),
+           ("polar_kernels.hip", ["POLAR_ED_TU=7"], ".adapt", []),
            ("polar_kernels_sc.hip", [], "", []), ("polar_kernels_p1.hip", [], "", []), ("polar_channel.hip", [], "", []),
            ("polar_construct.hip", [], "", []), ("polar_kernels_mlc.hip", [], "", []), ("polar_kernels_ga.hip", [], "", []),
-           ("polar_kernels_metric.hip", [], "", [])] + \
+           ("polar_kernels_metric.hip", [], "", []), ("polar_kernels_adapt.hip", [], "", [])] + \
           [(f, [], "", []) for f in ("polar_handle.cpp", "polar_decode.cpp", "polar_hostpipe.cpp", "polar_montecarlo.cpp", "polar_multi.cpp",
-                                     "polar_debug.cpp", "polar_ga.cpp", "polar_bicm.cpp", "polar_list.cpp", "polar_mlc.cpp")]
+                                     "polar_debug.cpp", "polar_ga.cpp", "polar_bicm.cpp", "polar_list.cpp", "polar_mlc.cpp", "polar_adaptive.cpp")]
 # the test build (libpolar_amd_test.so): the same objects, except that these two are compiled again with -DPOLAR_TEST_HOOKS —
 # the fault-injection keys of include/polar_amd_debug.h exist only there
 TEST_HOOK_SOURCES = ("polar_montecarlo.cpp", "polar_debug.cpp")

@@ -160,6 +160,70 @@ public:
         }
         return r;
     }
+    // Adaptive list decoding (polar_decode_scl_llr_adaptive_batch; B codewords back to back): the list sizes of `schedule` (strictly
+    // increasing, at most POLAR_AD_MAX_STAGES) in turn until the winner passes the CRC. out is decode_scl_llr's result at the list size
+    // schedule[stage[b]]; crc_ok = 0 only at the last stage. The code needs a CRC.
+    struct AdaptiveResult {
+        long B = 0;
+        int K = 0;
+        std::vector<uint8_t> out;        // [B][K]
+        std::vector<double> pm;          // [B]
+        std::vector<uint8_t> stage;      // [B]
+        std::vector<uint8_t> crc_ok;     // [B]
+    };
+    AdaptiveResult decode_scl_llr_adaptive(const std::vector<double> &llr, const std::vector<uint8_t> &schedule = {1, 4, 32}) {
+        need(llr.size() % _block_length == 0, "decode_scl_llr_adaptive: size must be a multiple of block_length");
+        AdaptiveResult r;
+        r.B = (long)(llr.size() / _block_length); r.K = _info_length;
+        r.out.resize((size_t)r.B * r.K); r.pm.resize((size_t)r.B); r.stage.resize((size_t)r.B); r.crc_ok.resize((size_t)r.B);
+        check(polar_decode_scl_llr_adaptive_batch(_h, llr.data(), POLAR_LLR_F64, r.B, schedule.data(), (int)schedule.size(), r.out.data(),
+                                                  r.pm.data(), r.stage.data(), r.crc_ok.data()));
+        return r;
+    }
+    // The adaptive decoder over a sweep (polar_mc_batch_adaptive in rounds, stopped like list_stats). stats is
+    // [point * (POLAR_AD_STAGE0 + n_stages) + POLAR_AD_*], stage_share [point * n_stages + stage]; mean_effort[point] = the mean over
+    // the trials of schedule[0] + ... + schedule[stage] (a fixed list of L costs L).
+    struct AdaptiveStats {
+        int n_points = 0, n_stages = 0;
+        std::vector<uint64_t> stats;
+        std::vector<double> bler, undetected_rate, stage_share, mean_effort;
+    };
+    AdaptiveStats adaptive_stats(const std::vector<double> &axis, const std::vector<uint8_t> &schedule, long max_runs = 1000,
+                                 long max_err = 100, uint64_t seed = 0, long batch = 0, int constellation = 0) {
+        need(max_runs >= 1 && batch >= 0, "adaptive_stats: max_runs must be positive and batch non-negative");
+        AdaptiveStats r;
+        r.n_points = (int)axis.size(); r.n_stages = (int)schedule.size();
+        const size_t P = axis.size(), C = (size_t)POLAR_AD_STAGE0 + schedule.size();
+        r.stats.assign(P * C, 0);
+        std::vector<uint8_t> enabled(P);
+        long done = 0, step = batch ? batch : (2 * max_err > 256 ? 2 * max_err : 256);
+        while (done < max_runs) {
+            bool any = false;
+            for (size_t i = 0; i < P; ++i) {
+                enabled[i] = (long)r.stats[i * C + POLAR_AD_ERR] <= max_err && (long)r.stats[i * C + POLAR_AD_RUN] < max_runs;
+                any = any || enabled[i];
+            }
+            if (!any) break;
+            const long T = step < max_runs - done ? step : max_runs - done;
+            check(polar_mc_batch_adaptive(_h, constellation, seed, (uint64_t)done, T, 1, axis.data(), r.n_points, schedule.data(),
+                                          r.n_stages, enabled.data(), r.stats.data()));
+            done += T;
+            if (!batch) step = 2 * step < 262144 ? 2 * step : 262144;
+        }
+        r.bler.resize(P); r.undetected_rate.resize(P); r.mean_effort.assign(P, 0.0); r.stage_share.resize(P * schedule.size());
+        for (size_t i = 0; i < P; ++i) {
+            const uint64_t *s = &r.stats[i * C];
+            const double run = s[POLAR_AD_RUN] ? (double)s[POLAR_AD_RUN] : 1.0;
+            r.bler[i] = s[POLAR_AD_ERR] / run; r.undetected_rate[i] = s[POLAR_AD_UNDET] / run;
+            double cost = 0.0;
+            for (size_t k = 0; k < schedule.size(); ++k) {
+                cost += schedule[k];
+                r.stage_share[i * schedule.size() + k] = s[POLAR_AD_STAGE0 + k] / run;
+                r.mean_effort[i] += r.stage_share[i * schedule.size() + k] * cost;
+            }
+        }
+        return r;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

@@ -277,7 +277,7 @@ void drop_clones(polar_code *h) {
 extern "C" {
 
 const char *polar_last_error(void) { return g_err.c_str(); }
-int polar_version(void) { return 100; }
+int polar_version(void) { return 200; }
 
 int polar_create(int n, int K, double eps, int crc, polar_code_t **out) {
     if (!out) return fail(POLAR_E_ARG, "out is NULL");
@@ -363,7 +363,7 @@ void polar_destroy(polar_code_t *h) {
     h->d_crc_mask.release(); h->d_tabs.release(); h->d_pre.release(); h->d_llr_scr.release(); h->d_c_scr.release(); h->d_hist_scr.release();
     h->d_in.release(); h->d_f32.release(); h->d_out.release(); h->d_bytes_a.release(); h->d_bytes_b.release();
     h->d_counter.release(); h->d_sel.release(); h->d_work.release();
-    h->d_ech.release(); h->d_flags.release(); h->d_list.release(); h->d_count.release(); h->d_bicm_llr.release(); h->d_list_out.release(); h->d_metric_scr.release();
+    h->d_ech.release(); h->d_flags.release(); h->d_list.release(); h->d_count.release(); h->d_bicm_llr.release(); h->d_list_out.release(); h->d_metric_scr.release(); h->d_adapt_ctl.release();
     h->d_alive[0].release(); h->d_alive[1].release(); h->d_nalive.release(); h->d_mc_ctr.release();
     for (auto &sl : h->mc_slots) { sl.list[0].release(); sl.list[1].release(); }
     h->d_slot_n.release();

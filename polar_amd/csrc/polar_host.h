@@ -8,6 +8,7 @@
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
 //   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev, path metric of given words,
 //                         the list statistics of the sweep (polar_mc_batch_list)
+//   polar_adaptive.cpp    adaptive list decoding: a schedule of list sizes, escalated until the CRC passes, and its sweep
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction
 //   polar_mc_schedule.h   the schedule of the pipelined rounds alone (standard library only: tests/test_mc_schedule.py runs it on a CPU)
@@ -263,6 +264,7 @@ struct polar_code {
     DevBuf<unsigned int> d_count;
     DevBuf<double> d_list_out;       // host-pointer list call: one chunk of list output (metrics, counts, winners, bits, CRC flags: polar_list.cpp)
     DevBuf<double> d_metric_scr;     // path metric of given words: the per-wave rows [grid][N] of the codes too long for LDS, and the sweep's sent-word metrics (polar_list.cpp)
+    DevBuf<unsigned int> d_adapt_ctl;// adaptive decode: the work counters and list lengths of its stages, zeroed by one memset per call (polar_adaptive.cpp)
     DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never

@@ -53,6 +53,16 @@ struct PolarListParams : PolarDecodeParams {
     int32_t *list_win;           // [B] device or nullptr
 };
 
+// The adaptive decode (polar_launch_decode_llr_adapt) takes the decode parameters with its own fields BEHIND them, for
+// the same reason. One launch is one STAGE of a schedule of list sizes: a codeword whose winner is an active path that passes the CRC,
+// or any codeword of the last stage, is delivered (`out`, `pm_out`, ad_stage, ad_crc); every decoded codeword gets its retry byte.
+struct PolarAdaptParams : PolarDecodeParams {
+    uint8_t *ad_retry;           // [B] device: 1 = decode this codeword again at the next list size, 0 = delivered; written for EVERY decoded codeword
+    uint8_t *ad_stage;           // [B] device or nullptr: the stage that delivered the codeword
+    uint8_t *ad_crc;             // [B] device or nullptr: 1 = the delivered word's path passed the CRC
+    int ad_s, ad_last;           // this stage's index; 1 = last stage (deliver whatever the winner is)
+};
+
 // The two-phase list decode (polar_head_plan.h) takes the decode parameters with the hand-over BEHIND them, like the list output:
 // the kernels of the other translation units keep their argument block. Phase A (polar_launch_decode_head_export: the groups of
 // 4 lanes, L = 4) decodes the leaves up to head_phi and writes the records, phase B (polar_launch_decode_head_import: the list of
@@ -85,6 +95,8 @@ size_t polar_decode_lat_lds_bytes(int N, int gs, int W);
 hipError_t polar_launch_decode_llr(const PolarDecodeParams &p, int gs, int lds_log, int pipe, int grid, bool ed, hipStream_t st);
 // every surviving path of every codeword (LLR-domain arithmetic, batch geometry, default tuning: LDS_LOG = 3, four waves per block)
 hipError_t polar_launch_decode_llr_list(const PolarListParams &p, int gs, int grid, hipStream_t st);
+// one stage of the adaptive decode (LLR-domain arithmetic, batch geometry, default tuning), over rows 0 .. B-1 or the work list of p
+hipError_t polar_launch_decode_llr_adapt(const PolarAdaptParams &p, int gs, int grid, hipStream_t st);
 hipError_t polar_launch_ed_front(const void *llr, int llr_fmt, double *ech, uint8_t *flags, const double *tabs, int N, long B, const unsigned *n_dev, hipStream_t st);
 hipError_t polar_launch_ed_collect(const uint8_t *flags, long B, const unsigned *n_dev, uint32_t *list, unsigned *count, hipStream_t st);
 
@@ -203,6 +215,10 @@ hipError_t polar_launch_path_metric(const PolarMetricParams &p, int grid, hipStr
 hipError_t polar_launch_list_classify(const uint8_t *cand, const double *pm, const uint8_t *crc_ok, const int32_t *n_active,
                                       const int32_t *winner, const uint8_t *sent, const double *pm_sent, long B, int L, int K,
                                       const unsigned int *n_dev, unsigned long long *ctr, hipStream_t st);
+// The counters of the adaptive sweep (include/polar_amd.h POLAR_AD_*, polar_kernels_adapt.hip): delivered words out [B][K] against the
+// sent info [B][K]; ctr[0 .. 3 + n_s) are ADDED to
+hipError_t polar_launch_adapt_classify(const uint8_t *out, const uint8_t *stage, const uint8_t *crc_ok, const uint8_t *sent, long B,
+                                       int K, int n_s, unsigned long long *ctr, hipStream_t st);
 // Monte-Carlo round on the device (PolarCode.cpp:728-742, 758-769): alive[i] = t0 + i*stride, *n = T
 hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T, hipStream_t st);
 // rows [0, min(B, *n_in)): block error iff decoded != sent; ctr[0] += block errors, ctr[1] += differing bits

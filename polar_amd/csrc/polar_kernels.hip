@@ -114,6 +114,12 @@ __device__ __forceinline__ double ch_narrow(const double *row, size_t i, int fmt
 #define POLAR_LIST_OUT 1
 #define scl_decode_llr_kernel scl_decode_llr_list_kernel
 #define POLAR_KPARAMS PolarListParams
+#elif defined(POLAR_ED_TU) && POLAR_ED_TU == 7
+// the adaptive unit: the same kernel text with the finish that delivers a codeword only when its winner passes the
+// CRC (or the stage is the last) and leaves a retry byte for the next stage, under a symbol of its own
+#define POLAR_ADAPT_OUT 1
+#define scl_decode_llr_kernel scl_decode_llr_adapt_kernel
+#define POLAR_KPARAMS PolarAdaptParams
 #elif defined(POLAR_ED_TU) && (POLAR_ED_TU == 5 || POLAR_ED_TU == 6)
 // the two-phase units (polar_head_plan.h): the same kernel text with a compile-time hand-over mode, under a symbol
 // of its own. POLAR_HEAD = 1 (unit 5, the groups of 4 lanes): the leaf loop ends at p.head_phi and every active path writes the
@@ -750,13 +756,14 @@ __global__ __launch_bounds__(256) void prefix_kernel(PolarDecodeParams p, int st
     }
 }
 
-// This file is compiled seven times (polar_amd/build.py): POLAR_ED_TU = 0 instantiates the LLR-domain kernels and
+// This file is compiled eight times (polar_amd/build.py): POLAR_ED_TU = 0 instantiates the LLR-domain kernels and
 // the small helper kernels, POLAR_ED_TU = 1 the exp-domain kernels of the groups of 4, 8, 16 and 64 lanes, POLAR_ED_TU = 2 the
 // exp-domain list of 32 — translation units that build in parallel, that one with its own scheduler options
 // (max-memory-clause strategy + the AMDGPU register-pressure trackers: +2.2 ... 3.8 % on the headline kernel, -11 % on the
 // groups of 8: build.py) —, POLAR_ED_TU = 3 the exp-domain one-codeword-per-wave (LAT) kernels, POLAR_ED_TU = 4 the
 // LLR-domain batch kernels with the list-output finish (every group size, default tuning only: DESIGN.md §8e), POLAR_ED_TU = 5 and 6
-// the two phases of the two-phase list of 32 (the 4-lane head that exports, the list of 32 that imports: DESIGN.md §3).
+// the two phases of the two-phase list of 32 (the 4-lane head that exports, the list of 32 that imports: DESIGN.md §3), POLAR_ED_TU = 7
+// the LLR-domain batch kernels with the adaptive finish (every group size, default tuning only: DESIGN.md §8g).
 #ifndef POLAR_ED_TU
 #define POLAR_ED_TU 0
 #endif
@@ -923,6 +930,27 @@ hipError_t polar_launch_decode_llr_list(const PolarListParams &p, int gs, int gr
         case 16: return launch_list<16>(p, grid, st);
         case 32: return launch_list<32>(p, grid, st);
         case 64: return launch_list<64>(p, grid, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+#elif POLAR_ED_TU == 7
+template <int GS>
+static hipError_t launch_adapt(const PolarAdaptParams &p, int grid, hipStream_t st) {
+    const int wpb = polar_decode_waves_per_block(0);
+    const size_t lds = polar_decode_lds_bytes(3, 0);
+    hipLaunchKernelGGL((scl_decode_llr_kernel<GS, 3, 0, false>), dim3(grid / wpb), dim3(64 * wpb), lds, st, p);
+    return hipGetLastError();
+}
+hipError_t polar_launch_decode_llr_adapt(const PolarAdaptParams &p, int gs, int grid, hipStream_t st) {
+    if (!p.out || !p.ad_retry || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
+    switch (gs) {
+        case 1: return launch_adapt<1>(p, grid, st);
+        case 2: return launch_adapt<2>(p, grid, st);
+        case 4: return launch_adapt<4>(p, grid, st);
+        case 8: return launch_adapt<8>(p, grid, st);
+        case 16: return launch_adapt<16>(p, grid, st);
+        case 32: return launch_adapt<32>(p, grid, st);
+        case 64: return launch_adapt<64>(p, grid, st);
         default: return hipErrorInvalidValue;
     }
 }

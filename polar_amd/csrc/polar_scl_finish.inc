@@ -108,6 +108,39 @@
             }
             wave_mem_fence();
         }
+#elif defined(POLAR_ADAPT_OUT)
+        {   // ---------------- one stage of the adaptive decode (DESIGN.md §8g) ----------------
+            static_assert(!ED && !LAT && !PIPE, "the adaptive unit instantiates the LLR-domain batch kernel only");
+            // accepted: the winner is an active path AND itself passes the CRC (the "no path passes, take the best anyway" winner of
+            // :640-643 is not). Group-uniform. A codeword that is neither accepted nor in the last stage writes nothing of its word —
+            // no history walk, no K byte stores —, only its retry byte.
+            const bool accepted = win_active && __shfl((int)pass, gbase + win, 64) != 0;
+            const bool deliver = accepted || p.ad_last != 0;
+            if (deliver) {
+                int cur = win;
+                for (int w = Wused - 1; w >= 0; --w) {
+                    g_tb[(size_t)w * CST + POLAR_CL] = g_hist[(size_t)w * CST + POLAR_CGB + cur];
+                    cur = (int)(g_horg[(size_t)w * CST + POLAR_CGB + cur] & (GS - 1));
+                }
+            }
+            wave_mem_fence();
+            if (valid && deliver) {
+                for (int b = lig; b < K; b += GS) {
+                    unsigned r = p.info_rank[b];
+                    uint32_t wd = g_tb[(size_t)(r >> 5) * CST + POLAR_CL];
+                    p.out[(size_t)cw * K + b] = win_active ? (uint8_t)((wd >> (r & 31)) & 1u) : (uint8_t)0;
+                }
+                if (lig == 0) {
+                    // (no winner row — the reference's never-activated path 0 —: no metric either, +inf like the list's padding)
+                    if (p.pm_out) p.pm_out[cw] = win_active ? pm_win : __builtin_inf();
+                    if (p.ad_stage) p.ad_stage[cw] = (uint8_t)p.ad_s;
+                    if (p.ad_crc) p.ad_crc[cw] = accepted ? (uint8_t)1 : (uint8_t)0;
+                }
+            }
+            // every decoded codeword, every stage: a byte left by an earlier stage or call is never read as current
+            if (valid && lig == 0) p.ad_retry[cw] = deliver ? (uint8_t)0 : (uint8_t)1;
+            wave_mem_fence();
+        }
 #else
         if (valid) {
 #if !defined(POLAR_PROFILE) && !defined(POLAR_SLOTHIST)
