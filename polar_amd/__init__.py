@@ -526,16 +526,38 @@ class PolarCode:
         """polar_mc_batch_list: the trials {t0 + i*stride : i < T} of every enabled (L, point) ADD to stats, uint64
         [len(L), len(axis), 5] = LS_RUN, LS_ERR, LS_MISS, LS_UNDET, LS_ML. constellation 0: BPSK, `axis` = Eb/N0 in dB; an
         ASK constellation: the BICM front end, `axis` = SNR in dB."""
-        ax = np.ascontiguousarray(axis, np.float64)
         Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        self._mc_batch_cells(self._L.polar_mc_batch_list, seed, t0, T, stride, axis, Ls, enabled, stats, constellation, LS_N, True)
+
+    def _mc_batch_cells(self, fn, seed, t0, T, stride, axis, Ls, enabled, stats, constellation, cols, per_L):
+        """polar_mc_batch_list / _adaptive: `cols` counters and one `enabled` byte per cell (a point; per_L: times a list size)."""
+        ax = np.ascontiguousarray(axis, np.float64)
         enabled = np.ascontiguousarray(enabled, np.uint8)
-        if stats.dtype != np.uint64 or stats.size != len(Ls) * len(ax) * LS_N or not stats.flags.c_contiguous:
-            raise PolarError("stats must be a C-contiguous uint64 array [len(L), len(axis), %d]" % LS_N)
-        if enabled.size != len(Ls) * len(ax):
-            raise PolarError("enabled must have len(L) * len(axis) entries")
-        self._chk(self._L.polar_mc_batch_list(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0),
-                                              C.c_long(T), C.c_long(stride), _p(ax, _dp), C.c_int(len(ax)), _p(Ls, _u8p),
-                                              C.c_int(len(Ls)), _p(enabled, _u8p), _p(stats, _u64p)))
+        cells, txt = (len(Ls) * len(ax), ("len(L)", "len(axis)")) if per_L else (len(ax), ("len(axis)",))
+        if stats.dtype != np.uint64 or stats.size != cells * cols or not stats.flags.c_contiguous:
+            raise PolarError("stats must be a C-contiguous uint64 array [%s, %d]" % (", ".join(txt), cols))
+        if enabled.size != cells:
+            raise PolarError("enabled must have %s entries" % " * ".join(txt))
+        self._chk(fn(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0), C.c_long(T), C.c_long(stride),
+                     _p(ax, _dp), C.c_int(len(ax)), _p(Ls, _u8p), C.c_int(len(Ls)), _p(enabled, _u8p), _p(stats, _u64p)))
+
+    @staticmethod
+    def _stat_rounds(who, batch_fn, stats, err_col, run_col, max_runs, max_err, batch):
+        """The rounds list_stats and adaptive_stats share: batch_fn(t0, T, enabled) ADDS the trials t0 .. t0 + T - 1 of the enabled
+        cells to `stats` ([..., columns]). `batch` trials a round; 0: max(256, 2 max_err) first, then doubling up to 262144. A cell
+        leaves once ERR > max_err or RUN >= max_runs; no round goes past max_runs; the rounds end when no cell is left."""
+        if max_runs < 1 or batch < 0:
+            raise PolarError(who + ": max_runs must be positive and batch non-negative")
+        done, step = 0, int(batch) if batch else max(256, 2 * int(max_err))
+        while done < max_runs:
+            enabled = ((stats[..., err_col] <= max_err) & (stats[..., run_col] < max_runs)).astype(np.uint8)
+            if not enabled.any():
+                break
+            T = min(step, max_runs - done)
+            batch_fn(done, T, enabled)
+            done += T
+            if not batch:
+                step = min(2 * step, 262144)
 
     def list_stats(self, axis, list_size_vec, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0):
         """Error analysis of the list decoder over a sweep: rounds of mc_batch_list (`batch` trials each; 0: max(256, 2 max_err)
@@ -544,19 +566,9 @@ class PolarCode:
         `undetected_rate`, `ml_bound` = ERR, MISS, UNDET, ML over RUN, float64 [len(L), len(axis)]."""
         ax = np.ascontiguousarray(axis, np.float64)
         Ls = np.ascontiguousarray(list_size_vec, np.uint8)
-        if max_runs < 1 or batch < 0:
-            raise PolarError("list_stats: max_runs must be positive and batch non-negative")
         stats = np.zeros((len(Ls), len(ax), LS_N), np.uint64)
-        done, step = 0, int(batch) if batch else max(256, 2 * int(max_err))
-        while done < max_runs:
-            enabled = ((stats[:, :, LS_ERR] <= max_err) & (stats[:, :, LS_RUN] < max_runs)).astype(np.uint8)
-            if not enabled.any():
-                break
-            T = min(step, max_runs - done)
-            self.mc_batch_list(seed, done, T, 1, ax, Ls, enabled, stats, constellation)
-            done += T
-            if not batch:
-                step = min(2 * step, 262144)
+        self._stat_rounds("list_stats", lambda t0, T, enabled: self.mc_batch_list(seed, t0, T, 1, ax, Ls, enabled, stats, constellation),
+                          stats, LS_ERR, LS_RUN, max_runs, max_err, batch)
         run = np.maximum(stats[:, :, LS_RUN], 1).astype(np.float64)
         res = {"stats": stats}
         for name, col in (("bler", LS_ERR), ("miss_rate", LS_MISS), ("undetected_rate", LS_UNDET), ("ml_bound", LS_ML)):
@@ -603,40 +615,21 @@ class PolarCode:
         """polar_mc_batch_adaptive: the trials {t0 + i*stride : i < T} of every enabled point ADD to stats, uint64
         [len(axis), 3 + len(schedule)] = AD_RUN, AD_ERR, AD_UNDET, then the trials delivered by each stage. constellation 0: BPSK,
         `axis` = Eb/N0 in dB; an ASK constellation: the BICM front end, `axis` = SNR in dB."""
-        ax = np.ascontiguousarray(axis, np.float64)
         Ls = self._schedule(schedule)
-        enabled = np.ascontiguousarray(enabled, np.uint8)
-        cols = AD_STAGE0 + len(Ls)
-        if stats.dtype != np.uint64 or stats.size != len(ax) * cols or not stats.flags.c_contiguous:
-            raise PolarError("stats must be a C-contiguous uint64 array [len(axis), %d]" % cols)
-        if enabled.size != len(ax):
-            raise PolarError("enabled must have len(axis) entries")
-        self._chk(self._L.polar_mc_batch_adaptive(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0),
-                                                  C.c_long(T), C.c_long(stride), _p(ax, _dp), C.c_int(len(ax)), _p(Ls, _u8p),
-                                                  C.c_int(len(Ls)), _p(enabled, _u8p), _p(stats, _u64p)))
+        self._mc_batch_cells(self._L.polar_mc_batch_adaptive, seed, t0, T, stride, axis, Ls, enabled, stats, constellation,
+                             AD_STAGE0 + len(Ls), False)
 
     def adaptive_stats(self, axis, schedule, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0):
-        """The adaptive decoder over a sweep: rounds of mc_batch_adaptive like list_stats' (`batch` trials each; 0: max(256,
-        2 max_err) first, then doubling up to 262144), a point leaves the sweep once ERR > max_err or RUN >= max_runs. Returns a
+        """The adaptive decoder over a sweep: rounds of mc_batch_adaptive, sized and stopped like list_stats' (_stat_rounds). Returns a
         dict: `stats` uint64 [len(axis), 3 + len(schedule)] (AD_* columns), `bler` and `undetected_rate` = ERR and UNDET over RUN
         [len(axis)], `stage_share` [len(axis), len(schedule)] = the share of the trials each stage delivered, and `mean_effort`
         [len(axis)] = the mean over the trials of schedule[0] + ... + schedule[stage]: the list sizes a codeword went through
         (a fixed list of L costs L)."""
         ax = np.ascontiguousarray(axis, np.float64)
         Ls = self._schedule(schedule)
-        if max_runs < 1 or batch < 0:
-            raise PolarError("adaptive_stats: max_runs must be positive and batch non-negative")
         stats = np.zeros((len(ax), AD_STAGE0 + len(Ls)), np.uint64)
-        done, step = 0, int(batch) if batch else max(256, 2 * int(max_err))
-        while done < max_runs:
-            enabled = ((stats[:, AD_ERR] <= max_err) & (stats[:, AD_RUN] < max_runs)).astype(np.uint8)
-            if not enabled.any():
-                break
-            T = min(step, max_runs - done)
-            self.mc_batch_adaptive(seed, done, T, 1, ax, Ls, enabled, stats, constellation)
-            done += T
-            if not batch:
-                step = min(2 * step, 262144)
+        self._stat_rounds("adaptive_stats", lambda t0, T, enabled: self.mc_batch_adaptive(seed, t0, T, 1, ax, Ls, enabled, stats, constellation),
+                          stats, AD_ERR, AD_RUN, max_runs, max_err, batch)
         run = np.maximum(stats[:, AD_RUN], 1).astype(np.float64)
         share = stats[:, AD_STAGE0:] / run[:, None]
         return {"stats": stats, "bler": stats[:, AD_ERR] / run, "undetected_rate": stats[:, AD_UNDET] / run, "stage_share": share,

@@ -131,26 +131,14 @@ public:
     };
     ListStats list_stats(const std::vector<double> &axis, const std::vector<uint8_t> &list_size, long max_runs = 1000, long max_err = 100,
                          uint64_t seed = 0, long batch = 0, int constellation = 0) {
-        need(max_runs >= 1 && batch >= 0, "list_stats: max_runs must be positive and batch non-negative");
         ListStats r;
         r.n_L = (int)list_size.size(); r.n_points = (int)axis.size();
         const size_t P = list_size.size() * axis.size();
         r.stats.assign(P * POLAR_LS_N, 0);
-        std::vector<uint8_t> enabled(P);
-        long done = 0, step = batch ? batch : (2 * max_err > 256 ? 2 * max_err : 256);
-        while (done < max_runs) {
-            bool any = false;
-            for (size_t i = 0; i < P; ++i) {
-                enabled[i] = (long)r.stats[i * POLAR_LS_N + POLAR_LS_ERR] <= max_err && (long)r.stats[i * POLAR_LS_N + POLAR_LS_RUN] < max_runs;
-                any = any || enabled[i];
-            }
-            if (!any) break;
-            const long T = step < max_runs - done ? step : max_runs - done;
-            check(polar_mc_batch_list(_h, constellation, seed, (uint64_t)done, T, 1, axis.data(), r.n_points, list_size.data(), r.n_L,
-                                      enabled.data(), r.stats.data()));
-            done += T;
-            if (!batch) step = 2 * step < 262144 ? 2 * step : 262144;
-        }
+        stat_rounds("list_stats", r.stats, POLAR_LS_N, POLAR_LS_ERR, POLAR_LS_RUN, max_runs, max_err, batch, [&](long t0, long T, const uint8_t *enabled) {
+            return polar_mc_batch_list(_h, constellation, seed, (uint64_t)t0, T, 1, axis.data(), r.n_points, list_size.data(), r.n_L,
+                                       enabled, r.stats.data());
+        });
         r.bler.resize(P); r.miss_rate.resize(P); r.undetected_rate.resize(P); r.ml_bound.resize(P);
         for (size_t i = 0; i < P; ++i) {
             const uint64_t *s = &r.stats[i * POLAR_LS_N];
@@ -190,26 +178,14 @@ public:
     };
     AdaptiveStats adaptive_stats(const std::vector<double> &axis, const std::vector<uint8_t> &schedule, long max_runs = 1000,
                                  long max_err = 100, uint64_t seed = 0, long batch = 0, int constellation = 0) {
-        need(max_runs >= 1 && batch >= 0, "adaptive_stats: max_runs must be positive and batch non-negative");
         AdaptiveStats r;
         r.n_points = (int)axis.size(); r.n_stages = (int)schedule.size();
         const size_t P = axis.size(), C = (size_t)POLAR_AD_STAGE0 + schedule.size();
         r.stats.assign(P * C, 0);
-        std::vector<uint8_t> enabled(P);
-        long done = 0, step = batch ? batch : (2 * max_err > 256 ? 2 * max_err : 256);
-        while (done < max_runs) {
-            bool any = false;
-            for (size_t i = 0; i < P; ++i) {
-                enabled[i] = (long)r.stats[i * C + POLAR_AD_ERR] <= max_err && (long)r.stats[i * C + POLAR_AD_RUN] < max_runs;
-                any = any || enabled[i];
-            }
-            if (!any) break;
-            const long T = step < max_runs - done ? step : max_runs - done;
-            check(polar_mc_batch_adaptive(_h, constellation, seed, (uint64_t)done, T, 1, axis.data(), r.n_points, schedule.data(),
-                                          r.n_stages, enabled.data(), r.stats.data()));
-            done += T;
-            if (!batch) step = 2 * step < 262144 ? 2 * step : 262144;
-        }
+        stat_rounds("adaptive_stats", r.stats, C, POLAR_AD_ERR, POLAR_AD_RUN, max_runs, max_err, batch, [&](long t0, long T, const uint8_t *enabled) {
+            return polar_mc_batch_adaptive(_h, constellation, seed, (uint64_t)t0, T, 1, axis.data(), r.n_points, schedule.data(),
+                                           r.n_stages, enabled, r.stats.data());
+        });
         r.bler.resize(P); r.undetected_rate.resize(P); r.mean_effort.assign(P, 0.0); r.stage_share.resize(P * schedule.size());
         for (size_t i = 0; i < P; ++i) {
             const uint64_t *s = &r.stats[i * C];
@@ -305,6 +281,28 @@ private:
     }
     static void need(bool ok, const char *msg) {
         if (!ok) throw std::out_of_range(msg);   // the reference throws out_of_range from .at()
+    }
+    // The rounds list_stats and adaptive_stats share: round(t0, T, enabled) adds the trials t0 .. t0 + T - 1 of the enabled cells to
+    // stats ([cell * cols + column]). `batch` trials a round; 0: max(256, 2 max_err), then doubling up to 262144. A cell leaves once
+    // ERR > max_err or RUN >= max_runs; no round goes past max_runs.
+    template <typename Round>
+    static void stat_rounds(const char *who, const std::vector<uint64_t> &stats, size_t cols, int err_col, int run_col, long max_runs, long max_err,
+                            long batch, Round round) {
+        need(max_runs >= 1 && batch >= 0, (std::string(who) + ": max_runs must be positive and batch non-negative").c_str());
+        std::vector<uint8_t> enabled(stats.size() / cols);
+        long done = 0, step = batch ? batch : (2 * max_err > 256 ? 2 * max_err : 256);
+        while (done < max_runs) {
+            bool any = false;
+            for (size_t i = 0; i < enabled.size(); ++i) {
+                enabled[i] = (long)stats[i * cols + err_col] <= max_err && (long)stats[i * cols + run_col] < max_runs;
+                any = any || enabled[i];
+            }
+            if (!any) break;
+            const long T = step < max_runs - done ? step : max_runs - done;
+            check(round(done, T, enabled.data()));
+            done += T;
+            if (!batch) step = 2 * step < 262144 ? 2 * step : 262144;
+        }
     }
     long bicm_rows(size_t n_sym, const std::string &name) const {
         const int id = constellation_id(name);

@@ -31,25 +31,17 @@ int adaptive_check(const polar_code *h, const void *llr, int fmt, long B, const 
 // the geometry of every stage of a call of B rows, and every buffer the launches use at its size — all of it BEFORE the first
 // launch: a DevBuf that grows frees what work in flight may still read
 int adaptive_prepare(polar_code *h, long B, const uint8_t *Ls, int n_s, BatchGeometry *g) {
-    int big = 0;
-    for (int s = 0; s < n_s; ++s) {
-        // (the grid of a later stage is sized for B as well: the host does not know how many codewords reach it; waves past the
-        // end of the work list leave at once)
+    // (the grid of a later stage is sized for B as well: the host does not know how many codewords reach it; waves past the end
+    // of the work list leave at once)
+    for (int s = 0; s < n_s; ++s)
         if (!batch_geometry(h, B, Ls[s], false, g[s])) return fail(POLAR_E_UNSUPPORTED, "the list kernel's LDS does not fit this device");
-        if (g[s].grid > g[big].grid) big = s;
-    }
-    // the per-wave state scratch for the largest grid (the stages are sequential and share it); a device too full for it runs fewer
-    // persistent waves
-    BatchGeometry gm = g[big];
     int rc;
-    while ((rc = ensure_batch_scratch(h, gm)) == POLAR_E_NOMEM && gm.grid > gm.wpb) {
-        (void)hipGetLastError();
-        gm.grid = std::max(gm.wpb, (gm.grid / 2 / gm.wpb) * gm.wpb);
-    }
-    if (rc) return rc;
-    for (int s = 0; s < n_s; ++s) g[s].grid = std::min(g[s].grid, gm.grid);
+    if ((rc = default_scratch(h, g, n_s))) return rc;                              // (the stages are sequential and share it)
     if ((rc = h->d_flags.ensure((size_t)B))) return rc;                            // retry bytes
     if ((rc = h->d_list.ensure((size_t)B))) return rc;                             // work list
+    PolarDecodeParams pp;                                                          // stage 0's prefix buffer
+    base_params(h, Ls[0], B, pp);
+    if ((rc = prefix_params(h, g[0].gs, pp))) return rc;
     return h->d_adapt_ctl.ensure(kCtlWords);
 }
 
@@ -102,77 +94,50 @@ int polar_decode_scl_llr_adaptive_batch(polar_code_t *h, const void *llr, int fm
     if (rc || B == 0) return rc;
     DevGuard dg_;
     if ((rc = ensure_device(h, dg_))) return rc;
-    const size_t row = (size_t)h->N * polar_llr_esz(fmt), K = (size_t)h->K;
-    if ((rc = h->d_in.ensure(((size_t)B * row + 7) / 8))) return rc;
+    const size_t K = (size_t)h->K;
+    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
     if ((rc = h->d_out.ensure((size_t)B * K))) return rc;
     if ((rc = h->d_bytes_b.ensure(2 * (size_t)B))) return rc;
     if ((rc = h->d_list_out.ensure((size_t)B))) return rc;
     uint8_t *d_stage = h->d_bytes_b.p, *d_crc = d_stage + B;
-    HIP_TRY(hipMemcpy(h->d_in.p, llr, (size_t)B * row, hipMemcpyHostToDevice));
     if ((rc = adaptive_launch(h, h->d_in.p, fmt, B, Ls, n_s, h->d_out.p, pm ? h->d_list_out.p : nullptr, stage ? d_stage : nullptr,
                               crc_ok ? d_crc : nullptr, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(out, h->d_out.p, (size_t)B * K, hipMemcpyDeviceToHost));
-    if (pm) HIP_TRY(hipMemcpy(pm, h->d_list_out.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost));
-    if (stage) HIP_TRY(hipMemcpy(stage, d_stage, (size_t)B, hipMemcpyDeviceToHost));
-    if (crc_ok) HIP_TRY(hipMemcpy(crc_ok, d_crc, (size_t)B, hipMemcpyDeviceToHost));
-    return POLAR_OK;
+    if ((rc = copy_back(out, 0, h->d_out.p, (size_t)B * K)) || (rc = copy_back(pm, 0, h->d_list_out.p, (size_t)B))) return rc;
+    if ((rc = copy_back(stage, 0, d_stage, (size_t)B))) return rc;
+    return copy_back(crc_ok, 0, d_crc, (size_t)B);
 }
 
 // Per enabled point and per chunk of trials, stream-ordered: the trials' LLRs and sent info (synth_kernel), the stages, the
 // classification. The counters stay on the device until the end.
 int polar_mc_batch_adaptive(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis,
                             int n_e, const uint8_t *Ls, int n_s, const uint8_t *enabled, uint64_t *stats) {
-    if (!h || !axis || !Ls || !enabled || !stats) return fail(POLAR_E_ARG, "NULL argument");
-    if (constellation & POLAR_RX_MLC) return fail(POLAR_E_ARG, "the adaptive decoder has no MLC receiver");
-    if (constellation != 0 && !is_ask_constellation(constellation)) return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
-    if (T < 0 || stride <= 0 || n_e <= 0) return fail(POLAR_E_ARG, "bad sizes");
-    if (int rc = schedule_check(Ls, n_s)) return rc;
-    if (h->crc == 0) return fail(POLAR_E_ARG, "adaptive decoding needs a CRC: this code has none to accept a word on");
-    if (T == 0) return POLAR_OK;
-    const int cid = constellation == POLAR_CONST_BPSK ? 0 : constellation;       // (BPSK on the Eb/N0 axis under either name)
-    DevGuard dg_;
-    int rc = ensure_device(h, dg_);
-    if (rc) return rc;
+    Sweep sw;
+    int rc = sweep_begin(sw, h, axis && Ls && enabled && stats, "adaptive decoder has", constellation, seed, t0, T, stride, axis, n_e > 0,
+                         stats, [&]() -> int {
+        if (int r = schedule_check(Ls, n_s)) return r;
+        return h->crc ? POLAR_OK : fail(POLAR_E_ARG, "adaptive decoding needs a CRC: this code has none to accept a word on");
+    });
+    if (rc || T == 0) return rc;
     const int N = h->N, K = h->K, C = POLAR_AD_STAGE0 + n_s;
     // a chunk: 512 MiB of LLR rows and their bytes, or the knob of the list calls
-    const size_t per = (size_t)N * sizeof(double) + 2 * (size_t)K + 2;
-    const long chunk = std::min<long>(T, h->knobs.list_chunk_cw > 0 ? h->knobs.list_chunk_cw : std::max<long>(1, (long)(((size_t)512 << 20) / per)));
+    const long chunk = chunk_len(h, T, (size_t)512 << 20, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
     // (every buffer at its largest before the first launch)
     BatchGeometry g[POLAR_AD_MAX_STAGES];
     if ((rc = adaptive_prepare(h, chunk, Ls, n_s, g))) return rc;
-    {
-        PolarDecodeParams pp;
-        base_params(h, Ls[0], chunk, pp);
-        if ((rc = prefix_params(h, g[0].gs, pp))) return rc;
-    }
     if ((rc = h->d_in.ensure((size_t)chunk * N))) return rc;
     if ((rc = h->d_bytes_a.ensure((size_t)chunk * K))) return rc;                // sent info
     if ((rc = h->d_out.ensure((size_t)chunk * K))) return rc;                    // delivered words
     if ((rc = h->d_bytes_b.ensure(2 * (size_t)chunk))) return rc;                // stage, crc_ok
-    if ((rc = h->d_mc_ctr.ensure((size_t)C * n_e))) return rc;
     uint8_t *d_stage = h->d_bytes_b.p, *d_crc = d_stage + chunk;
-    HIP_TRY(hipMemsetAsync(h->d_mc_ctr.p, 0, (size_t)C * n_e * sizeof(unsigned long long), nullptr));
-    for (int ie = 0; ie < n_e; ++ie) {
-        if (!enabled[ie]) continue;
-        for (long c0 = 0; c0 < T; c0 += chunk) {
-            const long c = std::min(chunk, T - c0);
-            PolarEncodeParams p;
-            fill_enc(h, p);
-            p.B = c; p.seed = seed; p.trial0 = t0 + (uint64_t)c0 * (uint64_t)stride; p.stride = stride;
-            fill_channel(h, p, cid, axis[ie]);
-            p.llr = h->d_in.p; p.info_out = h->d_bytes_a.p;
-            HIP_TRY(polar_launch_synth(p, nullptr));
-            if ((rc = adaptive_launch(h, h->d_in.p, POLAR_LLR_F64, c, Ls, n_s, h->d_out.p, nullptr, d_stage, d_crc, nullptr))) return rc;
-            HIP_TRY(polar_launch_adapt_classify(h->d_out.p, d_stage, d_crc, h->d_bytes_a.p, c, K, n_s, h->d_mc_ctr.p + (size_t)C * ie, nullptr));
-        }
-    }
-    std::vector<unsigned long long> ctr((size_t)C * n_e);
-    HIP_TRY(hipMemcpy(ctr.data(), h->d_mc_ctr.p, ctr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n_e; ++i)
-        if (enabled[i])
-            for (int k = 0; k < C; ++k) stats[(size_t)i * C + k] += (uint64_t)ctr[(size_t)i * C + k];
-    return POLAR_OK;
+    std::vector<SweepCell> cells;
+    for (int ie = 0; ie < n_e; ++ie)
+        if (enabled[ie]) cells.push_back({ie, chunk, (size_t)C * ie, C});
+    return sweep_walk(sw, cells, (size_t)C * n_e, [&](const SweepCell &cell, long c) -> int {
+        if (int r = adaptive_launch(h, h->d_in.p, POLAR_LLR_F64, c, Ls, n_s, h->d_out.p, nullptr, d_stage, d_crc, nullptr)) return r;
+        HIP_TRY(polar_launch_adapt_classify(h->d_out.p, d_stage, d_crc, h->d_bytes_a.p, c, K, n_s, h->d_mc_ctr.p + cell.ctr, nullptr));
+        return POLAR_OK;
+    });
 }
 
 }  // extern "C"

@@ -277,6 +277,18 @@ int polar_host::ensure_batch_scratch(polar_code *h, const BatchGeometry &g) {
     return h->d_hist_scr.ensure((size_t)g.grid * 3 * h->W * 64 + 64);
 }
 
+// batch_setup's counterpart at the default tuning (the geometries differ in their grid alone): no budget, the grid halved in whole blocks
+int polar_host::default_scratch(polar_code *h, BatchGeometry *g, int n) {
+    BatchGeometry gm = *std::max_element(g, g + n, [](const BatchGeometry &a, const BatchGeometry &b) { return a.grid < b.grid; });
+    int rc;
+    while ((rc = ensure_batch_scratch(h, gm)) == POLAR_E_NOMEM && gm.grid > gm.wpb) {
+        (void)hipGetLastError();
+        gm.grid = std::max(gm.wpb, (gm.grid / 2 / gm.wpb) * gm.wpb);
+    }
+    for (int s = 0; s < n && !rc; ++s) g[s].grid = std::min(g[s].grid, gm.grid);
+    return rc;
+}
+
 void polar_host::base_params(const polar_code *h, int L, long B, PolarDecodeParams &p) {
     p.n = h->n; p.N = h->N; p.K = h->K; p.crc = h->crc; p.L = L; p.W = h->W; p.B = B;
     p.prefix_q = 0; p.prefix_len = 0; p.pre = nullptr;

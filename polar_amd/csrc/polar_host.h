@@ -3,14 +3,15 @@
 //
 //   polar_handle.cpp      construction (the reference's constructor work), tables, device upload, getters / setters
 //   polar_decode.cpp      decode_scl_llr on the device: the family choice (choose_family), one launcher per kernel family behind
-//                         decode_impl, the device-resident entry points, P1 paths, encoder
+//                         decode_impl, the device-resident entry points, P1 paths, encoder; default_scratch (list output, adaptive)
 //   polar_mlc.cpp         MLC receiver: checks, parameter fill, dispatch of the multistage SC kernels, its entry points
 //   polar_hostpipe.cpp    host-pointer entry points: small-batch staging and the pipelined large-batch path
 //   polar_list.cpp        list output of decode_scl_llr (every surviving path), polar_list_find_dev, path metric of given words,
 //                         the list statistics of the sweep (polar_mc_batch_list)
 //   polar_adaptive.cpp    adaptive list decoding: a schedule of list sizes, escalated until the CRC passes, and its sweep
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
-//   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction
+//   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction;
+//                         the walk the sweeps of polar_list.cpp and polar_adaptive.cpp share (sweep_begin, sweep_walk)
 //   polar_mc_schedule.h   the schedule of the pipelined rounds alone (standard library only: tests/test_mc_schedule.py runs it on a CPU)
 //   polar_multi.cpp       multi-device context: RCCL binding, worker threads, watchdog, per-device clones
 //   polar_debug.cpp       measurement knobs (include/polar_amd_debug.h); fault injection only with -DPOLAR_TEST_HOOKS
@@ -356,6 +357,23 @@ int upload(DevBuf<T> &d, const std::vector<T> &v) {
     if (v.size()) HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return POLAR_OK;
 }
+// The host-pointer forms of the list output, the path metric and the adaptive decode: the caller's B rows of `fmt` staged in d_in
+// (whole doubles), and n results copied back to dst + at where the caller asked for them (after the stream was waited for)
+inline int stage_rows(polar_code *h, const void *rows, int fmt, long B) {
+    const size_t bytes = (size_t)B * h->N * polar_llr_esz(fmt);
+    if (int rc = h->d_in.ensure((bytes + 7) / 8)) return rc;
+    HIP_TRY(hipMemcpy(h->d_in.p, rows, bytes, hipMemcpyHostToDevice));
+    return POLAR_OK;
+}
+template <typename T>
+int copy_back(T *dst, size_t at, const T *d_src, size_t n) {
+    if (dst) HIP_TRY(hipMemcpy(dst + at, d_src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return POLAR_OK;
+}
+// codewords per chunk of a call of T: the list_chunk_cw knob, or what `budget` bytes hold at `per` bytes a codeword
+inline long chunk_len(const polar_code *h, long T, size_t budget, size_t per) {
+    return std::min<long>(T, h->knobs.list_chunk_cw > 0 ? h->knobs.list_chunk_cw : std::max<long>(1, (long)(budget / per)));
+}
 // The argument checks the entry points share, in the order the ABI pins: the pointers (`ptrs_set`: none is null), `mid` (the entry
 // point's own llr_fmt_check, bicm_check or mlc_check), the list size (kNoList: the call has none), the batch
 constexpr int kNoList = 1;
@@ -400,6 +418,9 @@ int decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long B, const uns
 struct BatchGeometry { int gs, G, wpc, lds_log, pipe, wpb, grid; size_t big, cwords; };
 bool batch_geometry(const polar_code *h, long B, int L, bool tuned, BatchGeometry &g);
 int ensure_batch_scratch(polar_code *h, const BatchGeometry &g);          // d_llr_scr, d_c_scr, d_hist_scr for g.grid waves
+// the scratch of n default-tuning launches that run one after the other and share it (the list output: one; the adaptive stages):
+// sized for the largest grid; a device too full for it runs fewer persistent waves — every g[i].grid is cut to what fits
+int default_scratch(polar_code *h, BatchGeometry *g, int n);
 // the ONE place the decode parameters are filled (tables, scratch, work counter; no prefix, optional pointers null): a caller adds its own
 void base_params(const polar_code *h, int L, long B, PolarDecodeParams &p);
 // the all-frozen prefix the batch kernels leave to prefix_kernel for groups of `gs` lanes: p.prefix_q / prefix_len / pre (d_pre grown)
@@ -420,6 +441,17 @@ void fill_demap(int cid, int N, double n0, PolarDemapParams &p);
 int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, long B, hipStream_t st, const double **d_llr);
 // polar_montecarlo.cpp — the channel of a sweep point in synth_kernel's parameters: BPSK at an Eb/N0 (constellation 0) or ASK / BICM at an SNR, both in dB
 void fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point);
+// The walk polar_mc_batch_list and polar_mc_batch_adaptive share. A cell: one enabled entry — its point of the axis, its chunk
+// length, its `width` counters at `ctr` in d_mc_ctr and in `stats`
+struct Sweep { polar_code *h; int cid; uint64_t seed, t0; long T, stride; const double *axis; uint64_t *stats; DevGuard dg; };
+struct SweepCell { int point; long chunk; size_t ctr; int width; };
+// the checks in the order the ABI pins (`ptrs_set`, "the `what` no MLC receiver", the constellation, `sizes_ok`, the caller's `own`);
+// past them with T > 0 the handle's device is current while `sw` lives (T == 0: POLAR_OK, nothing to do)
+int sweep_begin(Sweep &sw, polar_code *h, bool ptrs_set, const char *what, int constellation, uint64_t seed, uint64_t t0, long T,
+                long stride, const double *axis, bool sizes_ok, uint64_t *stats, const std::function<int()> &own);
+// n_ctr zeroed device counters; per cell and chunk of c trials: synth_kernel into d_in (LLR rows) and d_bytes_a (sent info), then
+// body(cell, c) — the null stream, buffers sized by the caller —; at the end the cells' counters ADD to stats
+int sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, size_t n_ctr, const std::function<int(const SweepCell &, long)> &body);
 // polar_hostpipe.cpp
 // rows that are received symbols instead of LLRs (polar_decode_bicm_batch*): M elements per row, demapped on the device
 struct SymRows { int cid, M; double n0; };

@@ -912,48 +912,38 @@ size_t polar_decode_lat_lds_bytes(int N, int gs, int W) {
 }
 #endif
 
-#if POLAR_ED_TU == 4
+#if POLAR_ED_TU == 4 || POLAR_ED_TU == 7
+// the finish variants of the LLR-domain batch kernel (POLAR_KPARAMS: list output, adaptive): every group size, default tuning only
 template <int GS>
-static hipError_t launch_list(const PolarListParams &p, int grid, hipStream_t st) {
+static hipError_t launch_finish(const POLAR_KPARAMS &p, int grid, hipStream_t st) {
     const int wpb = polar_decode_waves_per_block(0);
     const size_t lds = polar_decode_lds_bytes(3, 0);
     hipLaunchKernelGGL((scl_decode_llr_kernel<GS, 3, 0, false>), dim3(grid / wpb), dim3(64 * wpb), lds, st, p);
     return hipGetLastError();
 }
+static hipError_t launch_finish_gs(const POLAR_KPARAMS &p, int gs, int grid, hipStream_t st) {
+    switch (gs) {
+        case 1: return launch_finish<1>(p, grid, st);
+        case 2: return launch_finish<2>(p, grid, st);
+        case 4: return launch_finish<4>(p, grid, st);
+        case 8: return launch_finish<8>(p, grid, st);
+        case 16: return launch_finish<16>(p, grid, st);
+        case 32: return launch_finish<32>(p, grid, st);
+        case 64: return launch_finish<64>(p, grid, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+#if POLAR_ED_TU == 4
 hipError_t polar_launch_decode_llr_list(const PolarListParams &p, int gs, int grid, hipStream_t st) {
     if (!p.list_cand || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
-    switch (gs) {
-        case 1: return launch_list<1>(p, grid, st);
-        case 2: return launch_list<2>(p, grid, st);
-        case 4: return launch_list<4>(p, grid, st);
-        case 8: return launch_list<8>(p, grid, st);
-        case 16: return launch_list<16>(p, grid, st);
-        case 32: return launch_list<32>(p, grid, st);
-        case 64: return launch_list<64>(p, grid, st);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_finish_gs(p, gs, grid, st);
 }
-#elif POLAR_ED_TU == 7
-template <int GS>
-static hipError_t launch_adapt(const PolarAdaptParams &p, int grid, hipStream_t st) {
-    const int wpb = polar_decode_waves_per_block(0);
-    const size_t lds = polar_decode_lds_bytes(3, 0);
-    hipLaunchKernelGGL((scl_decode_llr_kernel<GS, 3, 0, false>), dim3(grid / wpb), dim3(64 * wpb), lds, st, p);
-    return hipGetLastError();
-}
+#else
 hipError_t polar_launch_decode_llr_adapt(const PolarAdaptParams &p, int gs, int grid, hipStream_t st) {
     if (!p.out || !p.ad_retry || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
-    switch (gs) {
-        case 1: return launch_adapt<1>(p, grid, st);
-        case 2: return launch_adapt<2>(p, grid, st);
-        case 4: return launch_adapt<4>(p, grid, st);
-        case 8: return launch_adapt<8>(p, grid, st);
-        case 16: return launch_adapt<16>(p, grid, st);
-        case 32: return launch_adapt<32>(p, grid, st);
-        case 64: return launch_adapt<64>(p, grid, st);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_finish_gs(p, gs, grid, st);
 }
+#endif
 #elif POLAR_ED_TU == 5
 // phase A of the two-phase list decode: the groups of 4 lanes, list size 4, up to p.head_phi (`grid` counts waves, whole blocks)
 hipError_t polar_launch_decode_head_export(const PolarHeadParams &p, int grid, hipStream_t st) {

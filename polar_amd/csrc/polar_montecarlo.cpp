@@ -20,6 +20,41 @@ void polar_host::fill_channel(const polar_code *h, PolarEncodeParams &p, int con
     }
 }
 
+// ---- the sweeps of the list statistics and of the adaptive decoder (polar_list.cpp, polar_adaptive.cpp) ----
+int polar_host::sweep_begin(Sweep &sw, polar_code *h, bool ptrs_set, const char *what, int constellation, uint64_t seed, uint64_t t0,
+                            long T, long stride, const double *axis, bool sizes_ok, uint64_t *stats, const std::function<int()> &own) {
+    if (!h || !ptrs_set) return fail(POLAR_E_ARG, "NULL argument");
+    if (constellation & POLAR_RX_MLC) return fail(POLAR_E_ARG, "the %s no MLC receiver", what);
+    if (constellation != 0 && !is_ask_constellation(constellation)) return fail(POLAR_E_ARG, "unknown constellation %d", constellation);
+    if (T < 0 || stride <= 0 || !sizes_ok) return fail(POLAR_E_ARG, "bad sizes");
+    if (int rc = own()) return rc;
+    sw.cid = constellation == POLAR_CONST_BPSK ? 0 : constellation;              // (BPSK on the Eb/N0 axis under either name)
+    sw.h = h; sw.seed = seed; sw.t0 = t0; sw.T = T; sw.stride = stride; sw.axis = axis; sw.stats = stats;
+    return T == 0 ? POLAR_OK : ensure_device(h, sw.dg);
+}
+
+int polar_host::sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, size_t n_ctr, const std::function<int(const SweepCell &, long)> &body) {
+    polar_code *h = sw.h;
+    if (int rc = h->d_mc_ctr.ensure(n_ctr)) return rc;
+    HIP_TRY(hipMemsetAsync(h->d_mc_ctr.p, 0, n_ctr * sizeof(unsigned long long), nullptr));
+    for (const SweepCell &cell : cells)
+        for (long c0 = 0; c0 < sw.T; c0 += cell.chunk) {
+            const long c = std::min(cell.chunk, sw.T - c0);
+            PolarEncodeParams p;
+            fill_enc(h, p);
+            p.B = c; p.seed = sw.seed; p.trial0 = sw.t0 + (uint64_t)c0 * (uint64_t)sw.stride; p.stride = sw.stride;
+            fill_channel(h, p, sw.cid, sw.axis[cell.point]);
+            p.llr = h->d_in.p; p.info_out = h->d_bytes_a.p;
+            HIP_TRY(polar_launch_synth(p, nullptr));
+            if (int rc = body(cell, c)) return rc;
+        }
+    std::vector<unsigned long long> ctr(n_ctr);
+    HIP_TRY(hipMemcpy(ctr.data(), h->d_mc_ctr.p, n_ctr * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (const SweepCell &cell : cells)
+        for (int k = 0; k < cell.width; ++k) sw.stats[cell.ctr + k] += (uint64_t)ctr[cell.ctr + k];
+    return POLAR_OK;
+}
+
 extern "C" {
 
 // One Monte-Carlo round of T trials {t0 + i*stride} for every enabled (L, Eb/N0) point, entirely stream-ordered on

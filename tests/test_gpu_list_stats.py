@@ -151,6 +151,25 @@ def test_sweep_points_list_sizes_and_a_disabled_cell(built_lib, oracle_built):
     assert stats[1, 0, LS.ERR] > stats[1, 1, LS.ERR]
 
 
+def test_sweep_cells_with_different_chunks_and_geometries(built_lib, oracle_built):
+    """One call whose list sizes take groups of 2, 8 and 32 lanes (with and without a prefix pass) in chunks of 7, 7, 7 and 2 trials:
+    every buffer is sized once for the largest before the first launch, and every cell counts what a call of its own counts."""
+    _, g = _pair(10, 512, 8)
+    T, Ls, axis = 23, [2, 8, 32], [1.0, 2.0]
+    en = np.array([[1, 1], [0, 1], [1, 1]], np.uint8)
+    g.debug_set("list_chunk_cw", 7)
+    try:
+        stats = np.full((3, 2, 5), 5, np.uint64)                           # (the call ADDS)
+        g.mc_batch_list(3, 0, T, 1, axis, Ls, en, stats)
+        alone = {(li, ie): _mc_list(g, T, [Ls[li]], [axis[ie]], seed=3)[0, 0] for li in range(3) for ie in range(2) if en[li, ie]}
+    finally:
+        g.debug_set("list_chunk_cw", 0)
+    assert (stats[1, 0] == 5).all()
+    for (li, ie), want in alone.items():
+        assert (stats[li, ie] - 5).tolist() == want.tolist(), (li, ie)
+        assert want[LS.RUN] == T
+
+
 # ---- 4. BICM ------------------------------------------------------------------------------------------------------------------
 def test_sweep_bicm(built_lib, oracle_built):
     import polar_amd

@@ -207,6 +207,40 @@ def test_formats_and_host_form(built_lib, oracle_built):
     assert (cand.cpu().numpy() == want[0]).all()
 
 
+# ---- the second call allocates nothing ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,K,crc", [(6, 32, 8), (10, 512, 8)])          # (10, 512, 8): a prefix pass in front of the groups of 8 lanes
+def test_second_call_allocates_nothing(built_lib, oracle_built, n, K, crc):
+    """The list call and the metric call size every buffer before their first launch (list_prepare): the same calls again find them in
+    place — no hipFree / hipMalloc, so nothing synchronises — and write the same bytes."""
+    import torch
+    _, g = _pair(n, K, crc)
+    B, L = 9, 8
+    t = torch.zeros(B * (1 << n), dtype=torch.float64, device="cuda")
+    g.synth_llr_dev(S.LIST_SEED, 0, B, g.snr_sqrt_linear(S.LIST_EBNO), t.data_ptr())
+    torch.cuda.synchronize()
+
+    def calls():
+        cand = torch.full((B, L, K), 7, dtype=torch.uint8, device="cuda")
+        pm = torch.full((B, L), -1.0, dtype=torch.float64, device="cuda")
+        ok = torch.full((B, L), 7, dtype=torch.uint8, device="cuda")
+        na = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+        win = torch.full((B,), -7, dtype=torch.int32, device="cuda")
+        forced = torch.full((B, L), -1.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        before = g.debug_get("allocs")
+        g.decode_scl_llr_list_dev(t.data_ptr(), "f64", B, L, cand.data_ptr(), pm.data_ptr(), ok.data_ptr(), na.data_ptr(), win.data_ptr())
+        g.path_metric_dev(t.data_ptr(), "f64", cand.data_ptr(), B, L, forced.data_ptr())
+        moved = g.debug_get("allocs") - before
+        torch.cuda.synchronize()
+        return moved, [x.cpu().numpy().tobytes() for x in (cand, pm, ok, na, win, forced)]
+    _, first = calls()
+    moved, second = calls()
+    assert moved == 0
+    assert second == first
+    na = np.frombuffer(first[3], np.int32)
+    assert ((1 <= na) & (na <= L)).all()                                   # (the calls decoded something)
+
+
 def test_list_find_dev(built_lib, oracle_built):
     import torch
     o, g = _pair(6, 32, 8)

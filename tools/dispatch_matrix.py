@@ -6,8 +6,9 @@
     python tools/dispatch_matrix.py compare <dir A> <dir B> > profiles/refactor/dispatch_trace.txt
 
 `run` makes a fixed matrix of calls on ONE handle of the N = 1024 code (10, 512, 8) — every kernel family of decode_scl_llr
-through the device-resident entry points (the twelve calls of tests/test_gpu_dispatch_sequence.py), one pipelined host batch
-and one short get_bler_quick — and prints one line per call. `compare` reads the two kernel traces in the order of submission
+through the device-resident entry points (the twelve calls of tests/test_gpu_dispatch_sequence.py), one pipelined host batch,
+one short get_bler_quick and the variants of the list decoder (adaptive, host-pointer list output in chunks, path metric, the two
+sweeps) — and prints one line per call. `compare` reads the two kernel traces in the order of submission
 and compares kernel name, grid, workgroup and LDS size dispatch by dispatch; exit status 1 if they differ.
 """
 import csv
@@ -68,6 +69,23 @@ def run(lib_path):
         g.debug_set(key, 0)
     bler = g.get_bler_quick([1.0, 2.0], [1, 4], max_runs=2000, max_err=20, seed=3)
     print("get_bler_quick", bler.tolist())
+    # the variants of the list decoder: adaptive, the host-pointer list call over a chunk boundary, the path metric, their sweeps
+    g.decode_scl_llr_adaptive_dev(buf.data_ptr(), "f64", 9, (1, 4, 32), out.data_ptr())
+    torch.cuda.synchronize()
+    print("adaptive schedule=(1, 4, 32) B=9")
+    g.debug_set("list_chunk_cw", 5)
+    lists = g.decode_scl_llr_list(llr[:9], 8)
+    print("host list L=8 B=9 list_chunk_cw=5")
+    g.path_metric(llr[:9], lists[0])
+    print("path_metric B=9 R=8")
+    g.debug_set("list_chunk_cw", 7)
+    stats = np.zeros((2, 2, polar_amd.LS_N), np.uint64)
+    g.mc_batch_list(3, 0, 23, 1, [1.0, 2.0], [2, 8], np.ones((2, 2), np.uint8), stats)
+    print("mc_batch_list T=23 L=(2, 8) list_chunk_cw=7", stats[:, :, :2].tolist())
+    stats = np.zeros((2, polar_amd.AD_STAGE0 + 3), np.uint64)
+    g.mc_batch_adaptive(3, 0, 23, 1, [1.0, 2.0], (1, 4, 32), np.ones(2, np.uint8), stats)
+    print("mc_batch_adaptive T=23 schedule=(1, 4, 32) list_chunk_cw=7", stats.tolist())
+    g.debug_set("list_chunk_cw", 0)
 
 
 def dispatches(d):
