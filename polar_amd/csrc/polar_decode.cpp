@@ -87,7 +87,7 @@ int decode_sc8(Call &c, bool lat) {
         sp.flag_words = fwords; sp.work = ctrl; sp.n_dev = c.n_dev;
         sp.flag_bytes = lat ? h->lat_flag_bytes : nullptr;
         if (c.ev_start) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_start, c.st));
-        HIP_TRY(lat ? polar_launch_sc_lat(sp, (int)std::min<long>(B, (long)h->num_cu * 4), c.st) : polar_launch_sc8_decode(sp, sgrid, c.st));
+        HIP_TRY(lat ? polar_launch_sc_lat(sp, lat_grid(h, std::min<long>(B, (long)h->num_cu * 4)), c.st) : polar_launch_sc8_decode(sp, sgrid, c.st));
         if (c.ev_stop) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_stop, c.st));
         if (c.phase == 1 && lat && c.deferred) { *c.deferred = Deferred::FlagWords; return POLAR_OK; }
     }
@@ -99,11 +99,13 @@ int decode_sc8(Call &c, bool lat) {
 // LDS (scl_decode_llr_kernel<.., LAT = 1>; exp-domain arithmetic for groups of 4 and 8 lanes, LLR-domain for groups of 2). The
 // kernel converts the channel itself (no conversion pass, no prefix kernel).
 // (groups of 2 lanes: the batch path is the LLR-domain kernel, but ONE codeword per wave is faster with the exp-domain nodes — 2.2
-// against 2.9 ms —, unless mode 1 forces the LLR-domain arithmetic, which flags nothing: no fallback pass, no batch geometry)
+// against 2.9 ms —, unless mode 1 forces the LLR-domain arithmetic, which flags nothing: no fallback pass, no batch geometry. A
+// requested path metric takes the LLR-domain form as well: the exp-domain leaf terms are -log(E) where the batch kernel of these
+// groups adds |llr|, one ulp apart on a third of the rows, and a row's metric must not depend on how many rows came with it)
 int decode_list_lat(const Call &c) {
     polar_code *h = c.h;
     const int gs = pow2ceil(c.L);
-    const bool ed = effective_mode(h) != 1;
+    const bool ed = effective_mode(h) != 1 && !(gs == 2 && c.d_pm);
     const long resident = lat_resident(h, gs);
     int rc;
     if (ed) {
@@ -119,7 +121,7 @@ int decode_list_lat(const Call &c) {
         if (ed) pl.flags = h->d_flags.p;
         HIP_TRY(hipMemsetAsync(p.work, 0, sizeof(unsigned int), c.st));
         if (c.ev_start) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_start, c.st));
-        HIP_TRY(polar_launch_decode_lat(pl, gs, ed, (int)std::min<long>(c.B, resident), c.st));
+        HIP_TRY(polar_launch_decode_lat(pl, gs, ed, lat_grid(h, std::min<long>(c.B, resident)), c.st));
         if (c.ev_stop) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_stop, c.st));
         if (ed && c.phase == 1 && c.deferred) { *c.deferred = Deferred::FlagBytes; return POLAR_OK; }
     }
@@ -315,6 +317,7 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long 
     if ((rc = ensure_device(h, dg_))) return rc;
     if ((rc = h->d_work.ensure(2))) return rc;
     h->last_head_phi = 0; h->last_head_b = 0;
+    if (phase != 2) h->last_lat_waves = 0;          // (phase 2 is the fallback pass of the same call: the launch was phase 1's)
     const Family fam = choose_family(h, B, L, d_pm != nullptr);
     Call c{h, d_llr, llr_fmt, B, n_dev, L, d_out, d_pm, (hipStream_t)stream, ev_start, ev_stop, phase, deferred, {}, {}};
     // (every family but one ends in a fallback pass of the batch kernel: the small lists in LLR-domain arithmetic flag nothing)
@@ -399,6 +402,7 @@ int polar_decode_sc_p1_batch(polar_code_t *h, const double *p1, long B, double *
     DevGuard dg_;
     if ((rc = ensure_device(h, dg_))) return rc;
     const int N = h->N;
+    h->last_lat_waves = 0;
     if ((rc = h->d_in.ensure((size_t)B * N + (size_t)B * h->K))) return rc;
     PolarScP1Params p;
     p.n = h->n; p.N = N; p.K = h->K; p.B = B;
@@ -411,7 +415,7 @@ int polar_decode_sc_p1_batch(polar_code_t *h, const double *p1, long B, double *
     const long lat_waves = polar_sc_p1_lat_lds_bytes(N) <= h->lds_per_block ? (long)h->num_cu * std::max<long>(1, (long)(h->lds_per_block / polar_sc_p1_lat_lds_bytes(N))) : 0;
     const long lat_max = h->knobs.lat_max_b < 0 ? 0 : (h->knobs.lat_max_b ? h->knobs.lat_max_b : lat_waves * 4);
     if (lat_waves > 0 && B <= lat_max) {
-        HIP_TRY(polar_launch_sc_p1_lat(p, (int)std::min<long>(B, lat_waves), nullptr));
+        HIP_TRY(polar_launch_sc_p1_lat(p, lat_grid(h, std::min<long>(B, lat_waves)), nullptr));
     } else {
         int grid = 1;
         rc = grid_that_fits(h, std::min<long>((B + 63) / 64, (long)h->num_cu * 16), (size_t)N * 64 * 4 * sizeof(double),

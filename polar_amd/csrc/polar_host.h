@@ -248,6 +248,7 @@ struct polar_code {
     DevBuf<unsigned long long> d_head_rec;   // two-phase list of 32: the hand-over records [B][rows][4] (polar_head_plan.h)
     int last_head_phi = 0;           //   hand-over leaf of the last decode_scl_llr call, 0 = one phase (polar_debug_get "head_phi")
     long last_head_b = 0;            //   ... and how many records it left (0: rows alive on the device only, Monte-Carlo): polar_debug_get "head_check"
+    long last_lat_waves = 0;         // blocks of the last one-codeword-per-wave launch of the last decode call, 0 = it took none (polar_debug_get "lat_waves")
     DevBuf<unsigned int> d_flag_words;
     DevBuf<double> d_llr_scr, d_tabs, d_pre;
     DevBuf<uint32_t> d_c_scr, d_hist_scr;
@@ -295,6 +296,7 @@ struct polar_code {
         long host_threads = 0;         // threads that copy between the caller's memory and the pinned slots (calling thread included)
         long host_ramp = 0;            // -1: no small first chunks (all chunks equal)
         long host_fail_alloc = 0;      // (test hook) the staging slot with this number (1-based) cannot be allocated
+        long lat_grid = 0;           //   at most this many blocks in a launch of theirs (0 = default: what the device holds); they loop over the rest
         long list_chunk_cw = 0;        // codewords per output chunk of the host-pointer list call (polar_list.cpp; 0 = default)
         long host_prefault = 0;        // threads that fault the caller's (fresh) output pages in while the first chunks decode (0 = default, -1 = none)
     } knobs;
@@ -369,6 +371,12 @@ template <typename T>
 int copy_back(T *dst, size_t at, const T *d_src, size_t n) {
     if (dst) HIP_TRY(hipMemcpy(dst + at, d_src, n * sizeof(T), hipMemcpyDeviceToHost));
     return POLAR_OK;
+}
+// blocks of a one-codeword-per-wave launch: the launch site's own grid under the "lat_grid" knob, remembered for "lat_waves"
+inline int lat_grid(polar_code *h, long grid) {
+    if (h->knobs.lat_grid > 0) grid = std::min<long>(grid, h->knobs.lat_grid);
+    h->last_lat_waves = grid;
+    return (int)grid;
 }
 // codewords per chunk of a call of T: the list_chunk_cw knob, or what `budget` bytes hold at `per` bytes a codeword
 inline long chunk_len(const polar_code *h, long T, size_t budget, size_t per) {

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
                 for (int k = 0; k < 8; ++k) {
                     const int i = i0 + 64 * k + lane;
                     double v = x[k];
-                    if constexpr (ED) { bool f; v = ed_from_channel(x[k], tb, f); any |= f; sized |= fabs(x[k]) >= 0.1; }
+                    if constexpr (ED) { bool f; v = ed_from_channel(x[k], tb, f); any |= f; sized |= i < N && fabs(x[k]) >= 0.1; }      // (i >= N: the padding 1.0 is no channel value)
                     if (i < N) lat_ch[__brev((unsigned)i) >> (32 - n)] = v;
                 }
             }

@@ -34,6 +34,7 @@ void polar_host::fill_mlc(const polar_code *h, int cid, double snr_db, PolarMlcP
 // of few waves cannot hide (N = 2048, B = 4096: 12.9 / 15.7 ms one lane per codeword, 8.8 / 7.0 ms one codeword per wave).
 int polar_host::mlc_decode_launch(polar_code *h, int cid, const double *d_y, double n0, long B, const unsigned int *n_dev,
                                   double *d_out, uint8_t *d_out_bytes, hipStream_t st) {
+    h->last_lat_waves = 0;
     PolarMlcParams p;
     fill_mlc(h, cid, 0.0, p);
     p.n0 = n0; p.B = B; p.n_dev = n_dev; p.y = const_cast<double *>(d_y); p.out = d_out; p.out_bytes = d_out_bytes;
@@ -41,7 +42,7 @@ int polar_host::mlc_decode_launch(polar_code *h, int cid, const double *d_y, dou
     const long lat_waves = lds <= h->lds_per_block ? (long)h->num_cu * std::max<long>(1, (long)(h->lds_per_block / lds)) : 0;
     const long lat_max = h->knobs.lat_max_b < 0 ? 0 : (h->knobs.lat_max_b ? h->knobs.lat_max_b : lat_waves * 8);
     if (lat_waves > 0 && B <= lat_max) {
-        HIP_TRY(polar_launch_mlc_sc_lat(p, (int)std::min<long>(B, lat_waves), st));
+        HIP_TRY(polar_launch_mlc_sc_lat(p, lat_grid(h, std::min<long>(B, lat_waves)), st));
     } else {
         const size_t per = polar_mlc_scr_doubles(h->N, p.nb);
         int grid = 1;

@@ -99,7 +99,10 @@ def test_fuzz_slice_latency_kernels(built_lib, oracle_built):
     """The one-codeword-per-wave kernels (round 4: list size 1 with the state in LDS; list sizes 2 ... 8 with the elements of
     every layer spread over the lanes of a path) on 80 random configurations a construction produces — block lengths 8 ... 4096,
     list sizes 1 ... 8 incl. 3, 5, 6, 7, CRCs, -1 ... 4.5 dB, degenerate rows mixed in — forced on whatever the batch size
-    ("lat_max_b"), against the oracle AND against the batch kernels: zero mismatching ordinary rows."""
+    ("lat_max_b"), against the oracle AND against the batch kernels: zero mismatching ordinary rows. Forcing is a request: the host
+    falls back to the batch kernel where the state does not fit the LDS, so the "lat_waves" hook is asked what ran. Up to N = 1024
+    the state is at most about 83 KB (polar_decode_lat_lds_bytes, groups of 8 lanes) and fits the 160 KiB of an MI355X: there the
+    latency kernel must have been taken; the total is printed."""
     import ctypes as C
     import polar_amd
     from oracle_lib import Oracle
@@ -123,15 +126,19 @@ def test_fuzz_slice_latency_kernels(built_lib, oracle_built):
         want = o.decode_scl_llr(llr, L)
         g.debug_set("lat_max_b", 1 << 40)
         got = g.decode_scl_llr(llr, L)
+        waves = g.debug_get("lat_waves")
+        used_lat += waves > 0
+        assert 0 <= waves <= B and (waves > 0 or N > 1024), (it, cfg, B, waves)
         g.debug_set("lat_max_b", -1)
         ref = g.decode_scl_llr(llr, L)
+        assert g.debug_get("lat_waves") == 0, (it, cfg, B)
         rows = np.nonzero((want != got).any(axis=1))[0]
         ordinary = [int(r) for r in rows if not (deg and r < 3)]
         total += B; bad += len(ordinary)
         if ordinary or (got != ref).any():
             fails.append((it, cfg, B, ordinary[:6], int((got != ref).any(axis=1).sum())))
         g.close()
-    print(f"latency-kernel fuzz slice: 80 configurations, {total} codewords, {bad} mismatching ordinary rows")
+    print(f"latency-kernel fuzz slice: 80 configurations ({used_lat} of them took a latency kernel), {total} codewords, {bad} mismatching ordinary rows")
     assert not fails, fails
 
 

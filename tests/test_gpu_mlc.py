@@ -63,9 +63,11 @@ def test_synth_and_decode_match_restatement(lib, const, N, src):
             g.debug_set("lat_max_b", lat)
             got = g.decode_mlc(y, n0, const)
             assert np.array_equal(got, want, equal_nan=True), (const, N, snr, lat)
+            assert (g.debug_get("lat_waves") > 0) == (lat > 0), (const, N, lat)       # (the forced leg did take the latency kernel)
             out = torch.empty((B, K), dtype=torch.float64, device="cuda")
             g.decode_mlc_dev(const, d_y.data_ptr(), n0, B, out.data_ptr())
             torch.cuda.synchronize()
+            assert (g.debug_get("lat_waves") > 0) == (lat > 0), (const, N, lat)
             assert np.array_equal(out.cpu().numpy(), want, equal_nan=True)
         g.debug_set("lat_max_b", 0)
     # encoder, and a noiseless decode returns the info

@@ -35,10 +35,16 @@ def test_tiny_block_lengths(built_lib, oracle_built, n, K):
 @pytest.mark.parametrize("n,K", [(11, 1024), (12, 2048), (13, 4096)])
 def test_lds_gate(built_lib, oracle_built, n, K):
     """The one-codeword-per-wave kernel's state is 4 N doubles + N bytes of LDS: two waves per CU at N = 2048, one at N = 4096;
-    N = 8192 does not fit, and forcing the kernel there must fall through to the lane kernel and still be right."""
+    N = 8192 does not fit, and forcing the kernel there must fall through to the lane kernel and still be right. The "lat_waves"
+    hook says which of the two the forced call took."""
     o, g = p1_rows.pair(n, K, 0)
     p1, _ = p1_rows.rows(o, 5, 1.0)
     _check(o, g, p1, (n, K))
+    g.debug_set("lat_max_b", 1 << 40)
+    g.decode_sc_p1(p1)
+    waves = g.debug_get("lat_waves")
+    g.debug_set("lat_max_b", 0)
+    assert (waves == 5) if n <= 12 else (waves == 0), (n, waves)
 
 
 def test_a_waves_second_and_third_codeword(built_lib, oracle_built):
