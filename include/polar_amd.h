@@ -258,7 +258,48 @@ int polar_mc_batch_adaptive(polar_code_t *h, int constellation, uint64_t seed, u
                             const double *axis, int n_e, const uint8_t *Ls, int n_s, const uint8_t *enabled /*[n_e]*/,
                             uint64_t *stats /*[n_e][3 + n_s], ADDED to*/);
 
-/* ---- PolarCode::decode_scl_p1 (PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
+/* ---- SC-Flip: CRC-aided single-bit retries of SC decoding (Afisiadis, Balatsoukas-Stimming, Burg 2014) ----
+ * (no member of the reference's class.) An SC pass with flip position c (c = -1: none) is plain successive cancellation in the LLR
+ * domain with the reference's node arithmetic (PolarCode.cpp:437-451); leaf phi — a position in decoding order, the index space of
+ * polar_get_frozen / polar_get_order — decides 0 if frozen, else 1 iff its LLR is negative, and at phi == c that decision is
+ * inverted. There is no path metric. With T = max_flips in 0 .. POLAR_FLIP_MAX and T_eff = min(T, K + crc):
+ *   pass 0   c = -1. Its unfrozen positions (info and check bits alike) ordered by |leaf LLR| ascending, equal magnitudes by position
+ *            ascending, give cand[0 .. T_eff) and their magnitudes mag[]. If the word passes the handle's CRC — the check bits the CRC
+ *            matrix gives for its K info bits equal its decided check bits — it is delivered: crc_ok = 1, n_dec = 1, flip = -1.
+ *   retry t  (t = 0 .. T_eff-1) a whole pass with c = cand[t]; the first word that passes is delivered: crc_ok = 1, n_dec = t + 2,
+ *            flip = cand[t].
+ *   no pass  pass 0's word: crc_ok = 0, n_dec = T_eff + 1, flip = -1.
+ *   out[B][K] uint8, crc_ok[B] uint8, n_dec[B] uint8, flip[B] int32, cand[B][max_flips] int32, mag[B][max_flips] double
+ * cand / mag are pass 0's and are written for every row; entries t >= T_eff are -1 / +inf. out / d_out is required, the other five may
+ * be NULL. Where the list-of-1 decode meets no tie between its two fork metrics, pass 0's word is polar_decode_scl_llr_batch_fmt(.., 1)
+ * in mode 1; max_flips = 0 is that decode with a CRC verdict. One kernel, one codeword per wave with its whole state in LDS: n <= 12
+ * (POLAR_E_UNSUPPORTED above, before the device is touched). polar_set_mode, polar_set_tuning and the latency threshold do not affect
+ * it. POLAR_E_ARG, before the device is touched: NULL handle / rows / out, max_flips out of range, a handle with crc == 0, unknown fmt,
+ * 16-bit rows at an odd address, negative B; B = 0 is POLAR_OK.
+ *   _dev   device pointers, stream-ordered on `stream`, no host synchronisation: ONE launch (the retries loop in the kernel). Two calls
+ *          on one handle and one stream need nothing between them. The first call of a handle uploads the kernel's schedule.
+ *   host   host pointers: one copy of all B rows in, the launch, a wait, the copies out. A convenience form like the list call's.
+ * polar_mc_batch_flip: like polar_mc_batch_adaptive: every ENABLED point of `axis` simulates all the trials {t0 + i*stride : i < T} and
+ * ADDS to stats[ie*POLAR_FL_N + c] (host uint64). `constellation` as polar_mc_batch_list; POLAR_RX_MLC, NULL pointers, max_flips out of
+ * range, crc == 0, negative T, stride < 1: POLAR_E_ARG before the device is touched; T = 0 is POLAR_OK and leaves stats alone. The
+ * trials run in chunks (512 MiB of LLR rows, or the "list_chunk_cw" knob); the counters are read once, at the end of the call. */
+#define POLAR_FLIP_MAX 64
+int polar_decode_sc_flip_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, int max_flips, uint8_t *d_out /*[B][K]*/,
+                                   uint8_t *d_crc_ok /*[B]*/, uint8_t *d_n_dec /*[B]*/, int32_t *d_flip /*[B]*/,
+                                   int32_t *d_cand /*[B][max_flips]*/, double *d_mag /*[B][max_flips]*/, void *stream);
+int polar_decode_sc_flip_batch(polar_code_t *h, const void *llr, int fmt, long B, int max_flips, uint8_t *out, uint8_t *crc_ok,
+                               uint8_t *n_dec, int32_t *flip, int32_t *cand, double *mag);
+#define POLAR_FL_RUN 0      /* every trial */
+#define POLAR_FL_ERR 1      /* delivered word differs from the sent info */
+#define POLAR_FL_UNDET 2    /* ERR and crc_ok = 1 */
+#define POLAR_FL_FIRST 3    /* crc_ok = 1 and n_dec == 1: pass 0 passed (with max_flips = 0 a failed word has n_dec = 1 too) */
+#define POLAR_FL_FLIPPED 4  /* crc_ok = 1 and n_dec > 1: a retry delivered */
+#define POLAR_FL_DECODES 5  /* sum of n_dec */
+#define POLAR_FL_N 6
+int polar_mc_batch_flip(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis,
+                        int n_e, int max_flips, const uint8_t *enabled /*[n_e]*/, uint64_t *stats /*[n_e][POLAR_FL_N], ADDED to*/);
+
+/* ---- PolarCode::decode_scl_p1(PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);
 

@@ -39,6 +39,8 @@ LLR_FORMATS = {"f64": LLR_F64, "f32": LLR_F32, "f16": LLR_F16, "bf16": LLR_BF16}
 LS_RUN, LS_ERR, LS_MISS, LS_UNDET, LS_ML, LS_N = 0, 1, 2, 3, 4, 5     # include/polar_amd.h POLAR_LS_*: columns of the list statistics
 AD_RUN, AD_ERR, AD_UNDET, AD_STAGE0 = 0, 1, 2, 3     # include/polar_amd.h POLAR_AD_*: columns of the adaptive statistics (+ one per stage)
 AD_MAX_STAGES = 8
+FL_RUN, FL_ERR, FL_UNDET, FL_FIRST, FL_FLIPPED, FL_DECODES, FL_N = 0, 1, 2, 3, 4, 5, 6     # include/polar_amd.h POLAR_FL_*: columns of the SC-Flip statistics
+FLIP_MAX = 64
 
 
 def _llr_fmt_code(fmt):
@@ -634,6 +636,67 @@ class PolarCode:
         share = stats[:, AD_STAGE0:] / run[:, None]
         return {"stats": stats, "bler": stats[:, AD_ERR] / run, "undetected_rate": stats[:, AD_UNDET] / run, "stage_share": share,
                 "mean_effort": share @ np.cumsum(Ls.astype(np.float64))}
+
+    def decode_sc_flip(self, llr, max_flips=8, fmt=None, return_candidates=False):
+        """SC-Flip (polar_decode_sc_flip_batch): one plain SC pass; while the word fails the CRC, whole re-decodes with one decision
+        inverted — the `max_flips` (0 .. 64) unfrozen leaves of smallest |LLR| of the first pass, least reliable first. Returns (out
+        [B, K] uint8, crc_ok [B] uint8, n_dec [B] uint8, flip [B] int32): the delivered word, whether it passed the CRC, the passes it
+        took and the flipped position in decoding order (-1: none). return_candidates=True adds (cand [B, max_flips] int32, mag
+        [B, max_flips] float64): pass 0's candidates and their magnitudes (-1 / inf past K + crc). `llr` and `fmt` as
+        decode_scl_llr_list; a single row [N] is a batch of one. The code needs a CRC; n <= 12."""
+        code, a = _llr_rows(llr, fmt)
+        a2 = a.reshape(-1, self.N)
+        B, T = a2.shape[0], int(max_flips)
+        out = np.zeros((B, self.K), np.uint8)
+        crc_ok = np.zeros(B, np.uint8)
+        n_dec = np.zeros(B, np.uint8)
+        flip = np.zeros(B, np.int32)
+        cand = np.zeros((B, max(T, 0)), np.int32)
+        mag = np.zeros((B, max(T, 0)), np.float64)
+        self._chk(self._L.polar_decode_sc_flip_batch(
+            self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), C.c_int(T), _p(out, _u8p), C.c_void_p(crc_ok.ctypes.data),
+            C.c_void_p(n_dec.ctypes.data), C.c_void_p(flip.ctypes.data), C.c_void_p(cand.ctypes.data if return_candidates else 0),
+            C.c_void_p(mag.ctypes.data if return_candidates else 0)))
+        return (out, crc_ok, n_dec, flip, cand, mag) if return_candidates else (out, crc_ok, n_dec, flip)
+
+    def decode_sc_flip_dev(self, llr_ptr, fmt, B, max_flips, out_ptr, crc_ok_ptr=0, n_dec_ptr=0, flip_ptr=0, cand_ptr=0, mag_ptr=0,
+                           stream=None):
+        """Device-resident form (polar_decode_sc_flip_batch_dev): LLRs [B, N] of format `fmt` -> out uint8 [B, K] and, where a pointer
+        is given, crc_ok uint8 [B], n_dec uint8 [B], flip int32 [B], cand int32 [B, max_flips], mag float64 [B, max_flips];
+        asynchronous on `stream`, one launch."""
+        self._chk(self._L.polar_decode_sc_flip_batch_dev(
+            self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B), C.c_int(max_flips), C.c_void_p(out_ptr),
+            C.c_void_p(crc_ok_ptr), C.c_void_p(n_dec_ptr), C.c_void_p(flip_ptr), C.c_void_p(cand_ptr), C.c_void_p(mag_ptr),
+            _stream_ptr(stream)))
+
+    def mc_batch_flip(self, seed, t0, T, stride, axis, max_flips, enabled, stats, constellation=0):
+        """polar_mc_batch_flip: the trials {t0 + i*stride : i < T} of every enabled point ADD to stats, uint64 [len(axis), 6] =
+        FL_RUN, FL_ERR, FL_UNDET, FL_FIRST, FL_FLIPPED, FL_DECODES. constellation 0: BPSK, `axis` = Eb/N0 in dB; an ASK constellation:
+        the BICM front end, `axis` = SNR in dB."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        enabled = np.ascontiguousarray(enabled, np.uint8)
+        if stats.dtype != np.uint64 or stats.size != len(ax) * FL_N or not stats.flags.c_contiguous:
+            raise PolarError("stats must be a C-contiguous uint64 array [len(axis), %d]" % FL_N)
+        if enabled.size != len(ax):
+            raise PolarError("enabled must have len(axis) entries")
+        self._chk(self._L.polar_mc_batch_flip(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0),
+                                              C.c_long(T), C.c_long(stride), _p(ax, _dp), C.c_int(len(ax)), C.c_int(max_flips),
+                                              _p(enabled, _u8p), _p(stats, _u64p)))
+
+    def flip_stats(self, axis, max_flips=8, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0):
+        """The SC-Flip decoder over a sweep: rounds of mc_batch_flip, sized and stopped like list_stats' (_stat_rounds). Returns a dict:
+        `stats` uint64 [len(axis), 6] (FL_* columns), `bler`, `undetected_rate`, `first_share`, `flipped_share` = ERR, UNDET, FIRST,
+        FLIPPED over RUN, and `mean_decodes` = DECODES over RUN: the SC passes a codeword took on average, all float64 [len(axis)]."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        stats = np.zeros((len(ax), FL_N), np.uint64)
+        self._stat_rounds("flip_stats", lambda t0, T, enabled: self.mc_batch_flip(seed, t0, T, 1, ax, max_flips, enabled, stats, constellation),
+                          stats, FL_ERR, FL_RUN, max_runs, max_err, batch)
+        run = np.maximum(stats[:, FL_RUN], 1).astype(np.float64)
+        res = {"stats": stats}
+        for name, col in (("bler", FL_ERR), ("undetected_rate", FL_UNDET), ("first_share", FL_FIRST), ("flipped_share", FL_FLIPPED),
+                          ("mean_decodes", FL_DECODES)):
+            res[name] = stats[:, col] / run
+        return res
 
     def decode_scl_llr_dev_f32(self, llr_ptr, B, list_size, out_ptr, pm_ptr=0, stream=None):
         """Device-resident float32 LLRs [B, N] -> uint8 [B, K]; asynchronous on `stream`."""

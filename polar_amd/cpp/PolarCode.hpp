@@ -200,6 +200,57 @@ public:
         }
         return r;
     }
+    // SC-Flip (polar_decode_sc_flip_batch; B codewords back to back): one plain SC pass; while the word fails the CRC, whole re-decodes
+    // with one decision inverted — the max_flips (0 .. POLAR_FLIP_MAX) unfrozen leaves of smallest |LLR| of the first pass, least
+    // reliable first. n_dec = the passes taken, flip = the inverted position in decoding order (-1: none); cand / mag: the first pass's
+    // candidates and their magnitudes (-1 / inf past K + crc). The code needs a CRC; block_length <= 4096.
+    struct FlipResult {
+        long B = 0;
+        int K = 0, max_flips = 0;
+        std::vector<uint8_t> out;        // [B][K]
+        std::vector<uint8_t> crc_ok;     // [B]
+        std::vector<uint8_t> n_dec;      // [B]
+        std::vector<int32_t> flip;       // [B]
+        std::vector<int32_t> cand;       // [B][max_flips]
+        std::vector<double> mag;         // [B][max_flips]
+    };
+    FlipResult decode_sc_flip(const std::vector<double> &llr, int max_flips = 8) {
+        need(llr.size() % _block_length == 0, "decode_sc_flip: size must be a multiple of block_length");
+        need(max_flips >= 0 && max_flips <= POLAR_FLIP_MAX, "decode_sc_flip: max_flips out of range");
+        FlipResult r;
+        r.B = (long)(llr.size() / _block_length); r.K = _info_length; r.max_flips = max_flips;
+        r.out.resize((size_t)r.B * r.K); r.crc_ok.resize((size_t)r.B); r.n_dec.resize((size_t)r.B); r.flip.resize((size_t)r.B);
+        r.cand.resize((size_t)r.B * max_flips); r.mag.resize((size_t)r.B * max_flips);
+        check(polar_decode_sc_flip_batch(_h, llr.data(), POLAR_LLR_F64, r.B, max_flips, r.out.data(), r.crc_ok.data(), r.n_dec.data(),
+                                         r.flip.data(), r.cand.data(), r.mag.data()));
+        return r;
+    }
+    // The SC-Flip decoder over a sweep (polar_mc_batch_flip in rounds, stopped like list_stats). stats is [point * POLAR_FL_N +
+    // POLAR_FL_*]; mean_decodes[point] = DECODES / RUN: the SC passes a codeword took on average.
+    struct FlipStats {
+        int n_points = 0;
+        std::vector<uint64_t> stats;
+        std::vector<double> bler, undetected_rate, first_share, flipped_share, mean_decodes;
+    };
+    FlipStats flip_stats(const std::vector<double> &axis, int max_flips = 8, long max_runs = 1000, long max_err = 100, uint64_t seed = 0,
+                         long batch = 0, int constellation = 0) {
+        FlipStats r;
+        r.n_points = (int)axis.size();
+        const size_t P = axis.size(), C = POLAR_FL_N;
+        r.stats.assign(P * C, 0);
+        stat_rounds("flip_stats", r.stats, C, POLAR_FL_ERR, POLAR_FL_RUN, max_runs, max_err, batch, [&](long t0, long T, const uint8_t *enabled) {
+            return polar_mc_batch_flip(_h, constellation, seed, (uint64_t)t0, T, 1, axis.data(), r.n_points, max_flips, enabled, r.stats.data());
+        });
+        r.bler.resize(P); r.undetected_rate.resize(P); r.first_share.resize(P); r.flipped_share.resize(P); r.mean_decodes.resize(P);
+        for (size_t i = 0; i < P; ++i) {
+            const uint64_t *s = &r.stats[i * C];
+            const double run = s[POLAR_FL_RUN] ? (double)s[POLAR_FL_RUN] : 1.0;
+            r.bler[i] = s[POLAR_FL_ERR] / run; r.undetected_rate[i] = s[POLAR_FL_UNDET] / run;
+            r.first_share[i] = s[POLAR_FL_FIRST] / run; r.flipped_share[i] = s[POLAR_FL_FLIPPED] / run;
+            r.mean_decodes[i] = s[POLAR_FL_DECODES] / run;
+        }
+        return r;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

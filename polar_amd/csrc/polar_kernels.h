@@ -219,6 +219,40 @@ hipError_t polar_launch_list_classify(const uint8_t *cand, const double *pm, con
 // sent info [B][K]; ctr[0 .. 3 + n_s) are ADDED to
 hipError_t polar_launch_adapt_classify(const uint8_t *out, const uint8_t *stage, const uint8_t *crc_ok, const uint8_t *sent, long B,
                                        int K, int n_s, unsigned long long *ctr, hipStream_t st);
+// SC-Flip (polar_kernels_flip.hip; include/polar_amd.h polar_decode_sc_flip_batch_dev): one codeword per wave, the whole
+// state in LDS (polar_flip_lds_bytes(N) must fit: N <= 2^polar_flip_max_log()). ops: the walk over the code tree without its all-frozen
+// subtrees, a word = type | lam << 3 | arg << 8 with lam the layer of the node the step produces (COMBINE: of the children) and arg
+// the left sibling's address residue (G), the parent's address residue (COMBINE), or for QUAD — a node of four leaves, layer n - 2 (PAIR: of two, the root of
+// n = 1) — the first leaf's position | the leaves' frozen bits << 16
+#define POLAR_FLIP_OP_F 0
+#define POLAR_FLIP_OP_G 1
+#define POLAR_FLIP_OP_PAIR 2
+#define POLAR_FLIP_OP_COMBINE 3
+#define POLAR_FLIP_OP_QUAD 4
+struct PolarFlipParams {
+    int n, N, K, crc, T;         // T: max_flips (the kernel clamps it to K + crc)
+    long B;
+    const void *llr;             // [B][N] device, elements of llr_fmt (POLAR_LLR_*)
+    int llr_fmt;
+    const uint32_t *ops;         // [n_ops] device
+    int n_ops;
+    const uint16_t *order;       // [N] device
+    const uint8_t *crcm;         // [crc][K] device
+    const double *tabs;          // [322] device
+    uint8_t *out;                // [B][K] device
+    uint8_t *crc_ok, *n_dec;     // [B] device or nullptr
+    int32_t *flip;               // [B] device or nullptr
+    int32_t *cand;               // [B][T] device or nullptr
+    double *mag;                 // [B][T] device or nullptr
+};
+size_t polar_flip_lds_bytes(int N);
+int polar_flip_max_log();
+int polar_flip_grid_cap();       // most blocks of a launch; the waves loop over the rest of the rows
+hipError_t polar_launch_sc_flip(const PolarFlipParams &p, int grid, hipStream_t st);
+// The counters of the SC-Flip sweep (include/polar_amd.h POLAR_FL_*): delivered words out [B][K] against the sent info [B][K];
+// ctr[0 .. POLAR_FL_N) are ADDED to
+hipError_t polar_launch_flip_classify(const uint8_t *out, const uint8_t *crc_ok, const uint8_t *n_dec, const uint8_t *sent, long B, int K,
+                                      unsigned long long *ctr, hipStream_t st);
 // Monte-Carlo round on the device (PolarCode.cpp:728-742, 758-769): alive[i] = t0 + i*stride, *n = T
 hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T, hipStream_t st);
 // rows [0, min(B, *n_in)): block error iff decoded != sent; ctr[0] += block errors, ctr[1] += differing bits
