@@ -46,6 +46,13 @@ int polar_debug_set(polar_code_t *h, const char *key, long value);
  * build); -1 = unknown key. Test build only: "head_check" reads the hand-over records of the handle's last two-phase decode back
  * and returns how many codewords did not arrive with the planned paths (0 = the premise holds; -2 = no records to read). */
 long polar_debug_get(const polar_code_t *h, const char *key);
+/* Which codewords the handle's last decode_scl_llr call on device pointers handed to its fallback pass (the fast kernels flag the rows
+ * whose decisions they cannot guarantee; the LLR-domain kernel decodes those again: DESIGN.md "Which rows take the fallback pass").
+ * Synchronises the call's stream, copies min(count, cap) row indices (in no particular order) to `rows` and returns the count.
+ * -1: the last call had no fallback pass (the LLR-domain families: lists of 1 with a path metric and of 2, mode 1; a pipelined
+ * host-pointer call; no call yet). Below -1: -(1 + the hipError_t that stopped it). The buffers are the handle's: the answer is
+ * valid until the next call on the handle. Both libraries. */
+long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap);
 /* number of ncclCommInitAll calls made by this library so far (the communicators of a device list are cached on the handle) */
 int polar_debug_comm_inits(void);
 /* older name of polar_get_weak_leaves (include/polar_amd.h) */

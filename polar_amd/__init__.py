@@ -238,6 +238,22 @@ class PolarCode:
         f.restype = C.c_long
         return int(f(self._h, key.encode()))
 
+    def debug_fallback_rows(self):
+        """The rows that the last decode_scl_llr call on device pointers handed to its fallback pass (polar_debug_fallback_rows), as a
+        sorted uint32 array; None if the call had no fallback pass. Synchronises the call's stream."""
+        f = self._L.polar_debug_fallback_rows
+        f.restype = C.c_long
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_long]
+        n = int(f(self._h, None, 0))
+        if n == -1:
+            return None
+        if n < 0:
+            raise PolarError(f"polar_debug_fallback_rows: HIP status {-n - 1}")
+        rows = np.zeros(max(n, 1), np.uint32)
+        if int(f(self._h, _p(rows, C.POINTER(C.c_uint32)), n)) != n:
+            raise PolarError("polar_debug_fallback_rows: the count changed between two reads")
+        return np.sort(rows[:n])
+
     @classmethod
     def from_block_length(cls, block_length, info_length, design_epsilon, crc_size=0):
         n = int(round(np.log2(block_length)))

@@ -121,4 +121,20 @@ long polar_debug_get(const polar_code_t *h, const char *key) {
 }
 int polar_debug_comm_inits(void) { return g_comm_inits.load(); }
 
+// The work list of the last call's fallback pass, read back from the handle's own buffers (nothing is copied per decode: the call
+// sites of fallback_pass leave the pointers, polar_decode.cpp). The count is capped by the call's batch: the list buffer holds
+// at least that many entries.
+long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap) {
+    if (!h || !h->fb_count) return -1;
+    DevGuard dg_;
+    if (ensure_device(h, dg_)) return -1;
+    hipError_t e = hipStreamSynchronize((hipStream_t)h->fb_stream);
+    unsigned int count = 0;
+    if (e == hipSuccess) e = hipMemcpy(&count, h->fb_count, sizeof count, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (long)count > h->fb_b) return -(long)hipErrorInvalidValue - 1;          // (a count no collect kernel can leave)
+    const long n = std::min<long>(count, cap);
+    if (e == hipSuccess && rows && n > 0) e = hipMemcpy(rows, h->fb_list, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? (long)count : -(long)e - 1;
+}
+
 }  // extern "C"

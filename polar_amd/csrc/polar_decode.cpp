@@ -92,6 +92,7 @@ int decode_sc8(Call &c, bool lat) {
         if (c.phase == 1 && lat && c.deferred) { *c.deferred = Deferred::FlagWords; return POLAR_OK; }
     }
     HIP_TRY(polar_launch_sc_collect(fwords, B, c.n_dev, h->d_list.p, ctrl + 1, c.st));
+    h->note_fallback(ctrl + 1, h->d_list.p, c.st, B);
     return fallback_pass(c.p, g, h->d_list.p, ctrl + 1, ctrl + 2, 16 * g.wpb, c.st);
 }
 
@@ -128,6 +129,7 @@ int decode_list_lat(const Call &c) {
     if (!ed) return POLAR_OK;
     HIP_TRY(hipMemsetAsync(h->d_count.p, 0, sizeof(unsigned int), c.st));
     HIP_TRY(polar_launch_ed_collect(h->d_flags.p, c.B, c.n_dev, h->d_list.p, h->d_count.p, c.st));
+    h->note_fallback(h->d_count.p, h->d_list.p, c.st, c.B);
     return fallback_pass(p, c.g, h->d_list.p, h->d_count.p, nullptr, 64 * c.g.wpb, c.st);
 }
 
@@ -205,6 +207,7 @@ int decode_batch_ed(Call &c) {
     if (c.ev_stop) HIP_TRY(hipEventRecord((hipEvent_t)c.ev_stop, c.st));
     HIP_TRY(polar_launch_ed_collect(h->d_flags.p, B, c.n_dev, h->d_list.p, h->d_count.p, c.st));
     // (normally empty: a few blocks; a code with weak unfrozen leaves may send most of its codewords here)
+    h->note_fallback(h->d_count.p, h->d_list.p, c.st, B);
     return fallback_pass(p, g, h->d_list.p, h->d_count.p, nullptr, h->weak_leaves ? g.grid : 64 * g.wpb, c.st);
 }
 
@@ -318,6 +321,7 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long 
     if ((rc = h->d_work.ensure(2))) return rc;
     h->last_head_phi = 0; h->last_head_b = 0;
     if (phase != 2) h->last_lat_waves = 0;          // (phase 2 is the fallback pass of the same call: the launch was phase 1's)
+    if (phase != 2) h->note_fallback(nullptr, nullptr, nullptr, 0);
     const Family fam = choose_family(h, B, L, d_pm != nullptr);
     Call c{h, d_llr, llr_fmt, B, n_dev, L, d_out, d_pm, (hipStream_t)stream, ev_start, ev_stop, phase, deferred, {}, {}};
     // (every family but one ends in a fallback pass of the batch kernel: the small lists in LLR-domain arithmetic flag nothing)

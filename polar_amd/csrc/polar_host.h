@@ -250,6 +250,13 @@ struct polar_code {
     int last_head_phi = 0;           //   hand-over leaf of the last decode_scl_llr call, 0 = one phase (polar_debug_get "head_phi")
     long last_head_b = 0;            //   ... and how many records it left (0: rows alive on the device only, Monte-Carlo): polar_debug_get "head_check"
     long last_lat_waves = 0;         // blocks of the last one-codeword-per-wave launch of the last decode call, 0 = it took none (polar_debug_get "lat_waves")
+    // the work list the last decode_impl call handed to fallback_pass (polar_debug_fallback_rows): device pointers into the handle's
+    // own buffers, the call's stream and batch; fb_count == nullptr: the last call had no fallback pass
+    const unsigned int *fb_count = nullptr;
+    const uint32_t *fb_list = nullptr;
+    void *fb_stream = nullptr;
+    long fb_b = 0;
+    void note_fallback(const unsigned int *count, const uint32_t *list, void *st, long B) { fb_count = count; fb_list = list; fb_stream = st; fb_b = B; }
     DevBuf<unsigned int> d_flag_words;
     DevBuf<double> d_llr_scr, d_tabs, d_pre;
     DevBuf<uint32_t> d_c_scr, d_hist_scr;

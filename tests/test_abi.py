@@ -31,6 +31,7 @@ def test_exports_every_declared_symbol(built_lib):
     from polar_amd import build
     api, dbg = _declared("polar_amd.h"), _declared("polar_amd_debug.h")
     assert len(api) >= 25 and "polar_debug_set" in dbg and not [n for n in api if n.startswith("polar_debug")]
+    assert "polar_debug_fallback_rows" in dbg
     assert "polar_amd_debug.h" not in re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "polar_amd.h")).read(), flags=re.S)
     for path in (built_lib, build.build_test()):
         lib = C.CDLL(path)
@@ -58,10 +59,12 @@ def test_fault_injection_exists_only_in_the_test_build(built_lib):
     with pytest.raises(polar_amd.PolarError, match="lat_grid"):
         g.debug_set("lat_grid", -1)
     assert g.debug_get("lat_waves") == 0                                # (a key of both libraries: no decode call yet)
+    assert g.debug_fallback_rows() is None                              # (polar_debug_fallback_rows: -1 before any decode call)
     try:
         polar_amd.use_library(build.build_test())
         t = polar_amd.PolarCode(5, 16, 0.32, 0)
         assert t.debug_get("test_hooks") == 1
+        assert t.debug_get("lat_waves") == 0 and t.debug_fallback_rows() is None
         for k in hooks + knobs:
             t.debug_set(k, 0)
         t.close()
