@@ -25,6 +25,9 @@ extern "C" {
  *   "lat_max_b"                   largest batch that takes the one-codeword-per-wave kernels (0 = default, -1 = never)
  *   "lat_grid"                    at most this many blocks in a launch of those kernels (0 = default: what the device holds); a wave
  *                                 then decodes further codewords in turn, whatever the device's CU count
+ *   "lane_grid"                   at most this many blocks in a codeword-per-lane launch of decode_scl_p1 / decode_sc_p1 / decode_mlc (and
+ *                                 the MLC sweep); 0 = default: 16 waves per CU. The per-wave scratch is sized for the capped grid, and a
+ *                                 wave then decodes further codewords in turn on the same scratch
  *   "host_pipe_min_bytes", "host_chunk_bytes", "host_lanes", "host_threads", "host_ramp", "host_prefault"
  *                                 the pipelined host-pointer path (0 = default everywhere)
  *   "list_chunk_cw"               codewords per output chunk of polar_decode_scl_llr_list_batch (0 = default: 256 MiB of list output)
@@ -40,7 +43,8 @@ int polar_debug_set(polar_code_t *h, const char *key, long value);
 /* polar_debug_get(h, key): "allocs" (hipMalloc calls of all handles' scratch so far), "comm_inits", "weak_leaves",
  * "mode_override", "head_phi" (hand-over leaf of the handle's last decode_scl_llr launch, 0 = decoded in one phase),
  * "lat_waves" (blocks of the one-codeword-per-wave launch of the handle's last decode_scl_llr / decode_sc_p1 / decode_mlc call, 0 = it
- * took no such kernel, or was a pipelined host-pointer call, whose chunks are decoded on contexts of their own), "last_rounds", "last_round_max_per_device", "worker_threads_started", "multi_poisoned",
+ * took no such kernel, or was a pipelined host-pointer call, whose chunks are decoded on contexts of their own), "lane_waves" (blocks of
+ * the codeword-per-lane launch of the handle's last decode_scl_p1 / decode_sc_p1 / decode_mlc call, 0 = it launched none), "last_rounds", "last_round_max_per_device", "worker_threads_started", "multi_poisoned",
  * "round_us_first|min|median|max|count" (steps of the handle's last sweep), "host_chunks", "host_chunk_cw", "host_lanes",
  * "host_threads", "host_us_copy_in|wait|copy_out|total" (the last pipelined host-pointer call), "test_hooks" (1 in the test
  * build); -1 = unknown key. Test build only: "head_check" reads the hand-over records of the handle's last two-phase decode back

@@ -34,6 +34,7 @@ int polar_debug_set(polar_code_t *h, const char *key, long value) {
 #endif
     else if (s == "lat_max_b") k.lat_max_b = value;
     else if (s == "lat_grid") { if (value < 0) return fail(POLAR_E_ARG, "lat_grid must be >= 0 (0 = default)"); k.lat_grid = value; }
+    else if (s == "lane_grid") { if (value < 0) return fail(POLAR_E_ARG, "lane_grid must be >= 0 (0 = default)"); k.lane_grid = value; }
     else if (s == "list_chunk_cw") { if (value < 0) return fail(POLAR_E_ARG, "list_chunk_cw must be >= 0"); k.list_chunk_cw = value; }
     else if (s == "host_pipe_min_bytes") k.host_pipe_min_bytes = value;
     else if (s == "host_chunk_bytes") k.host_chunk_bytes = value;
@@ -71,6 +72,7 @@ long polar_debug_get(const polar_code_t *h, const char *key) {
     if (s == "mode_override") return h->knobs.mode_override;
     if (s == "head_phi") return h->last_head_phi;
     if (s == "lat_waves") return h->last_lat_waves;
+    if (s == "lane_waves") return h->last_lane_waves;
 #ifdef POLAR_TEST_HOOKS
     if (s == "head_check") {
         // The premise of the two-phase decode, checked on what the head really left: row 2 of every record of the handle's last

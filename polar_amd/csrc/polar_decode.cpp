@@ -320,6 +320,7 @@ int polar_host::decode_impl(polar_code *h, const void *d_llr, int llr_fmt, long 
     if ((rc = ensure_device(h, dg_))) return rc;
     if ((rc = h->d_work.ensure(2))) return rc;
     h->last_head_phi = 0; h->last_head_b = 0;
+    if (phase != 2) h->last_lane_waves = 0;
     if (phase != 2) h->last_lat_waves = 0;          // (phase 2 is the fallback pass of the same call: the launch was phase 1's)
     if (phase != 2) h->note_fallback(nullptr, nullptr, nullptr, 0);
     const Family fam = choose_family(h, B, L, d_pm != nullptr);
@@ -377,7 +378,8 @@ int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p
     if ((rc = h->d_in.ensure((size_t)B * N * 2))) return rc;
     if ((rc = h->d_out.ensure((size_t)B * h->K))) return rc;
     int grid = 1;
-    rc = grid_that_fits(h, std::min<long>(groups, (long)h->num_cu * 16), (size_t)N * 64 * 2 * sizeof(double), [&](int g) {
+    h->last_lat_waves = 0; h->last_lane_waves = 0;
+    rc = grid_that_fits(h, lane_grid(h, std::min<long>(groups, (long)h->num_cu * 16)), (size_t)N * 64 * 2 * sizeof(double), [&](int g) {
         int r = h->d_llr_scr.ensure((size_t)g * N * 64 * 2 + 64);
         if (!r) r = h->d_c_scr.ensure((size_t)g * 2 * polar_decode_cwords(N) * 64 + 64);
         if (!r) r = h->d_hist_scr.ensure((size_t)g * h->W * 64 + 64);
@@ -391,6 +393,7 @@ int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p
     p.ctl = nullptr; p.work = nullptr;          // (the probability-domain kernel has no leaf schedule and no dynamic hand-out)
     p.llr = h->d_in.p; p.p0 = h->d_in.p + (size_t)B * N; p.out = h->d_out.p;
     HIP_TRY(polar_launch_decode_p1(p, gs, grid, nullptr));
+    h->last_lane_waves = grid;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, h->d_out.p, (size_t)B * h->K, hipMemcpyDeviceToHost));
     return POLAR_OK;
@@ -406,7 +409,7 @@ int polar_decode_sc_p1_batch(polar_code_t *h, const double *p1, long B, double *
     DevGuard dg_;
     if ((rc = ensure_device(h, dg_))) return rc;
     const int N = h->N;
-    h->last_lat_waves = 0;
+    h->last_lat_waves = 0; h->last_lane_waves = 0;
     if ((rc = h->d_in.ensure((size_t)B * N + (size_t)B * h->K))) return rc;
     PolarScP1Params p;
     p.n = h->n; p.N = N; p.K = h->K; p.B = B;
@@ -422,11 +425,12 @@ int polar_decode_sc_p1_batch(polar_code_t *h, const double *p1, long B, double *
         HIP_TRY(polar_launch_sc_p1_lat(p, lat_grid(h, std::min<long>(B, lat_waves)), nullptr));
     } else {
         int grid = 1;
-        rc = grid_that_fits(h, std::min<long>((B + 63) / 64, (long)h->num_cu * 16), (size_t)N * 64 * 4 * sizeof(double),
+        rc = grid_that_fits(h, lane_grid(h, std::min<long>((B + 63) / 64, (long)h->num_cu * 16)), (size_t)N * 64 * 4 * sizeof(double),
                             [&](int g) { return h->d_llr_scr.ensure((size_t)g * 4 * N * 64 + 64); }, &grid);
         if (rc) return rc;
         p.scr = h->d_llr_scr.p;
         HIP_TRY(polar_launch_sc_p1(p, grid, nullptr));
+        h->last_lane_waves = grid;
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, p.out, (size_t)B * h->K * sizeof(double), hipMemcpyDeviceToHost));

@@ -250,6 +250,7 @@ struct polar_code {
     int last_head_phi = 0;           //   hand-over leaf of the last decode_scl_llr call, 0 = one phase (polar_debug_get "head_phi")
     long last_head_b = 0;            //   ... and how many records it left (0: rows alive on the device only, Monte-Carlo): polar_debug_get "head_check"
     long last_lat_waves = 0;         // blocks of the last one-codeword-per-wave launch of the last decode call, 0 = it took none (polar_debug_get "lat_waves")
+    long last_lane_waves = 0;        // blocks of the last codeword-per-lane launch sized by grid_that_fits (decode_scl_p1 / decode_sc_p1 / decode_mlc), 0 = the last call had none (polar_debug_get "lane_waves")
     // the work list the last decode_impl call handed to fallback_pass (polar_debug_fallback_rows): device pointers into the handle's
     // own buffers, the call's stream and batch; fb_count == nullptr: the last call had no fallback pass
     const unsigned int *fb_count = nullptr;
@@ -308,6 +309,7 @@ struct polar_code {
         long host_ramp = 0;            // -1: no small first chunks (all chunks equal)
         long host_fail_alloc = 0;      // (test hook) the staging slot with this number (1-based) cannot be allocated
         long lat_grid = 0;           //   at most this many blocks in a launch of theirs (0 = default: what the device holds); they loop over the rest
+        long lane_grid = 0;          // at most this many blocks in a launch sized by grid_that_fits (0 = default: 16 waves per CU); the waves loop over the rest
         long list_chunk_cw = 0;        // codewords per output chunk of the host-pointer list call (polar_list.cpp; 0 = default)
         long host_prefault = 0;        // threads that fault the caller's (fresh) output pages in while the first chunks decode (0 = default, -1 = none)
     } knobs;
@@ -388,6 +390,10 @@ inline int lat_grid(polar_code *h, long grid) {
     if (h->knobs.lat_grid > 0) grid = std::min<long>(grid, h->knobs.lat_grid);
     h->last_lat_waves = grid;
     return (int)grid;
+}
+// waves a codeword-per-lane launch asks grid_that_fits for: the launch site's own count under the "lane_grid" knob
+inline long lane_grid(const polar_code *h, long want) {
+    return h->knobs.lane_grid > 0 ? std::min<long>(want, h->knobs.lane_grid) : want;
 }
 // codewords per chunk of a call of T: the list_chunk_cw knob, or what `budget` bytes hold at `per` bytes a codeword
 inline long chunk_len(const polar_code *h, long T, size_t budget, size_t per) {

@@ -200,6 +200,7 @@ int polar_host::host_decode(polar_code_t *h, const void *llr, int llr_fmt, const
     if (rc || B == 0) return rc;
     DevGuard dg_;
     if ((rc = ensure_device(h, dg_))) return rc;
+    h->last_lane_waves = 0;
     h->last_lat_waves = 0;          // (a pipelined call decodes on the lanes' own contexts: it reports none)
     h->note_fallback(nullptr, nullptr, nullptr, 0);
     // Symbol rows: the thresholds and chunk sizes below were fitted to LLR bytes, so they are applied to the LLR bytes the symbols

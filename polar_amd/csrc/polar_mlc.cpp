@@ -34,7 +34,7 @@ void polar_host::fill_mlc(const polar_code *h, int cid, double snr_db, PolarMlcP
 // of few waves cannot hide (N = 2048, B = 4096: 12.9 / 15.7 ms one lane per codeword, 8.8 / 7.0 ms one codeword per wave).
 int polar_host::mlc_decode_launch(polar_code *h, int cid, const double *d_y, double n0, long B, const unsigned int *n_dev,
                                   double *d_out, uint8_t *d_out_bytes, hipStream_t st) {
-    h->last_lat_waves = 0;
+    h->last_lat_waves = 0; h->last_lane_waves = 0;
     PolarMlcParams p;
     fill_mlc(h, cid, 0.0, p);
     p.n0 = n0; p.B = B; p.n_dev = n_dev; p.y = const_cast<double *>(d_y); p.out = d_out; p.out_bytes = d_out_bytes;
@@ -46,11 +46,12 @@ int polar_host::mlc_decode_launch(polar_code *h, int cid, const double *d_y, dou
     } else {
         const size_t per = polar_mlc_scr_doubles(h->N, p.nb);
         int grid = 1;
-        int rc = grid_that_fits(h, std::min<long>((B + 63) / 64, (long)h->num_cu * 16), per * sizeof(double),
+        int rc = grid_that_fits(h, lane_grid(h, std::min<long>((B + 63) / 64, (long)h->num_cu * 16)), per * sizeof(double),
                                 [&](int g) { return h->d_llr_scr.ensure((size_t)g * per + 64); }, &grid);
         if (rc) return rc;
         p.scr = h->d_llr_scr.p;
         HIP_TRY(polar_launch_mlc_sc(p, grid, st));
+        h->last_lane_waves = grid;
     }
     return POLAR_OK;
 }

@@ -48,7 +48,7 @@ def test_fault_injection_exists_only_in_the_test_build(built_lib):
     import polar_amd
     from polar_amd import build
     hooks = ("share_device", "fail_device", "fail_collective", "force_workers", "stall_device", "stall_ms")
-    knobs = ("mode_override", "lat_max_b", "lat_grid", "host_lanes", "host_prefault", "no_rccl", "multi_timeout_s")
+    knobs = ("mode_override", "lat_max_b", "lat_grid", "lane_grid", "host_lanes", "host_prefault", "no_rccl", "multi_timeout_s")
     g = polar_amd.PolarCode(5, 16, 0.32, 0)
     assert g.debug_get("test_hooks") == 0
     for k in hooks:
@@ -58,13 +58,16 @@ def test_fault_injection_exists_only_in_the_test_build(built_lib):
         g.debug_set(k, 0)
     with pytest.raises(polar_amd.PolarError, match="lat_grid"):
         g.debug_set("lat_grid", -1)
+    with pytest.raises(polar_amd.PolarError, match="lane_grid"):
+        g.debug_set("lane_grid", -1)
     assert g.debug_get("lat_waves") == 0                                # (a key of both libraries: no decode call yet)
+    assert g.debug_get("lane_waves") == 0
     assert g.debug_fallback_rows() is None                              # (polar_debug_fallback_rows: -1 before any decode call)
     try:
         polar_amd.use_library(build.build_test())
         t = polar_amd.PolarCode(5, 16, 0.32, 0)
         assert t.debug_get("test_hooks") == 1
-        assert t.debug_get("lat_waves") == 0 and t.debug_fallback_rows() is None
+        assert t.debug_get("lat_waves") == 0 and t.debug_get("lane_waves") == 0 and t.debug_fallback_rows() is None
         for k in hooks + knobs:
             t.debug_set(k, 0)
         t.close()
