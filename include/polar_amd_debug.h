@@ -20,6 +20,7 @@ extern "C" {
  *   "mode_override" -1|0|1|2      replaces polar_set_mode's value (-1 = none); POLAR_MODE in the environment at creation
  *   "sc_no_fold", "no_tables", "no_fuse_front", "no_prefix"     alternative (older) forms of single passes, for A/B timing
  *   "no_head"                     lists of 17 .. 32 in one phase: no 4-lane head in front of the list kernel (POLAR_NO_HEAD at creation)
+ *   "no_r1"                       control words without the rate-1 block field: the list-of-32 kernels take every leaf of such a block as a step of its own (POLAR_NO_R1 at creation)
  *   "head_min_b"                  smallest batch that takes the head (0 = default: from 16 codewords per resident wave on)
  *   "no_rccl", "force_rccl"       counter reduction of the single-process multi-device driver (drops its cached context)
  *   "lat_max_b"                   largest batch that takes the one-codeword-per-wave kernels (0 = default, -1 = never)
@@ -57,6 +58,11 @@ long polar_debug_get(const polar_code_t *h, const char *key);
  * host-pointer call; no call yet). Below -1: -(1 + the hipError_t that stopped it). The buffers are the handle's: the answer is
  * valid until the next call on the handle. Both libraries. */
 long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap);
+/* The per-leaf control words as uploaded (marked != 0: with the rate-1 block field in bits 9-10, else the plain array the knob
+ * "no_r1" selects): copies min(N, cap) words, returns N; below 0: -(1 + hipError_t). Both libraries. polar_debug_get
+ * "r1_committed" / "r1_discarded" (test build only): the rate-1 quad continuations the last list-of-32 launch of the handle's
+ * last call finished in one step / gave up, counted per wave. */
+long polar_debug_ctl_words(polar_code_t *h, uint32_t *words, long cap, int marked);
 /* number of ncclCommInitAll calls made by this library so far (the communicators of a device list are cached on the handle) */
 int polar_debug_comm_inits(void);
 /* older name of polar_get_weak_leaves (include/polar_amd.h) */

@@ -254,6 +254,17 @@ class PolarCode:
             raise PolarError("polar_debug_fallback_rows: the count changed between two reads")
         return np.sort(rows[:n])
 
+    def debug_ctl_words(self, marked=True):
+        """The per-leaf control words as uploaded (polar_debug_ctl_words): the array with the rate-1 block field, or the plain one."""
+        f = self._L.polar_debug_ctl_words
+        f.restype = C.c_long
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_long, C.c_int]
+        words = np.zeros(self.N, np.uint32)
+        n = int(f(self._h, _p(words, C.POINTER(C.c_uint32)), self.N, 1 if marked else 0))
+        if n != self.N:
+            raise PolarError(f"polar_debug_ctl_words: {n}")
+        return words
+
     @classmethod
     def from_block_length(cls, block_length, info_length, design_epsilon, crc_size=0):
         n = int(round(np.log2(block_length)))

@@ -37,9 +37,11 @@ SOURCES = [("polar_kernels.hip", ["POLAR_ED_TU=0"], "", []), ("polar_kernels.hip
            ("polar_kernels_flip.hip", [], "", [])] + \
           [(f, [], "", []) for f in ("polar_handle.cpp", "polar_decode.cpp", "polar_hostpipe.cpp", "polar_montecarlo.cpp", "polar_multi.cpp",
                                      "polar_debug.cpp", "polar_ga.cpp", "polar_bicm.cpp", "polar_list.cpp", "polar_mlc.cpp", "polar_adaptive.cpp", "polar_flip.cpp")]
-# the test build (libpolar_amd_test.so): the same objects, except that these two are compiled again with -DPOLAR_TEST_HOOKS —
+# the test build (libpolar_amd_test.so): the same objects, except that these are compiled again with -DPOLAR_TEST_HOOKS —
 # the fault-injection keys of include/polar_amd_debug.h exist only there
 TEST_HOOK_SOURCES = ("polar_montecarlo.cpp", "polar_debug.cpp")
+# ... and the list-of-32 units of polar_kernels.hip (object tags): their rate-1 continuation counters (polar_debug_get "r1_committed")
+TEST_HOOK_KERNEL_TAGS = (".ed32", ".headB")
 LIB_TEST = os.path.join(HERE, "libpolar_amd_test.so")
 # what POLAR_DEFS may name: instrumentation (measures, does not decode), trimmed development builds (fewer instantiations),
 # and the few A/B switches still open (same bits either way)
@@ -171,7 +173,7 @@ def build(force=False, verbose=False, profile=False, bless=False, test_hooks=Fal
     jobs = []
     for s, defs, otag, xflags in SOURCES:
         src = os.path.join(CSRC, s)
-        if test_hooks and s in TEST_HOOK_SOURCES:
+        if test_hooks and (s in TEST_HOOK_SOURCES or (s == "polar_kernels.hip" and otag in TEST_HOOK_KERNEL_TAGS)):
             defs, otag = defs + ["POLAR_TEST_HOOKS"], otag + ".th"
         obj = os.path.join(BUILD, s + otag + tag + ".o")
         objs.append(obj)

@@ -6,6 +6,9 @@
 #include "polar_amd_debug.h"
 #ifdef POLAR_TEST_HOOKS
 #include "polar_head_plan.h"
+// (polar_kernels.hip, units 2 and 6 of the test library: the continuation counters of the unit's last launch)
+hipError_t polar_r1_counts_read_ed32(unsigned long long *out);
+hipError_t polar_r1_counts_read_head(unsigned long long *out);
 #endif
 
 extern "C" {
@@ -20,6 +23,7 @@ int polar_debug_set(polar_code_t *h, const char *key, long value) {
     else if (s == "sc_no_fold") k.sc_no_fold = value != 0;
     else if (s == "no_tables") k.no_tables = value != 0;
     else if (s == "no_head") k.no_head = value != 0;
+    else if (s == "no_r1") k.no_r1 = value != 0;
     else if (s == "head_min_b") { if (value < 0) return fail(POLAR_E_ARG, "head_min_b must be >= 0 (0 = default)"); k.head_min_b = value; }
     else if (s == "no_fuse_front") k.no_fuse_front = value != 0;
     else if (s == "no_prefix") h->prefix_on = (value == 0);          // (the all-frozen prefix decoded leaf by leaf by the list kernel itself)
@@ -95,6 +99,13 @@ long polar_debug_get(const polar_code_t *h, const char *key) {
         }
         return bad;
     }
+    if (s == "r1_committed" || s == "r1_discarded") {
+        // rate-1 quad continuations of the last list-of-32 launch (the unit the handle's last call took: the two-phase import or
+        // the single-phase kernel): finished in one step / given up. The caller has synchronised the call's stream.
+        unsigned long long c[2] = {0, 0};
+        if ((h->last_head_phi ? polar_r1_counts_read_head(c) : polar_r1_counts_read_ed32(c)) != hipSuccess) return -2;
+        return (long)c[s == "r1_discarded" ? 1 : 0];
+    }
 #endif
     if (s == "last_rounds") return h->last_rounds;
     if (s == "last_round_max_per_device") return h->last_round_max_per_device;
@@ -137,6 +148,20 @@ long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap) {
     const long n = std::min<long>(count, cap);
     if (e == hipSuccess && rows && n > 0) e = hipMemcpy(rows, h->fb_list, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
     return e == hipSuccess ? (long)count : -(long)e - 1;
+}
+
+// The control words as they were uploaded (marked != 0: the array with the rate-1 block field, else the plain one): copies
+// min(N, cap) words to `words`, returns N; below 0: -(1 + hipError_t). Both libraries.
+long polar_debug_ctl_words(polar_code_t *h, uint32_t *words, long cap, int marked) {
+    if (!h) return -1;
+    DevGuard dg_;
+    if (ensure_device(h, dg_)) return -1;
+    const long n = std::min<long>(h->N, cap);
+    if (words && n > 0) {
+        const hipError_t e = hipMemcpy(words, marked ? h->d_ctl_r1.p : h->d_ctl.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return -(long)e - 1;
+    }
+    return h->N;
 }
 
 }  // extern "C"

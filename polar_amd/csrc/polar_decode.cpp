@@ -299,7 +299,7 @@ void polar_host::base_params(const polar_code *h, int L, long B, PolarDecodePara
     p.prefix_q = 0; p.prefix_len = 0; p.pre = nullptr;
     p.llr = nullptr; p.llr_fmt = POLAR_LLR_F64; p.p0 = nullptr; p.out = nullptr; p.pm_out = nullptr;
     p.frozen = h->d_frozen.p; p.info_rank = h->d_info_rank.p; p.crc_mask = h->d_crc_mask.p; p.tabs = h->d_tabs.p;
-    p.ctl = h->d_ctl.p; p.work = h->d_work.p; p.llr_scr = h->d_llr_scr.p; p.c_scr = h->d_c_scr.p; p.hist_scr = h->d_hist_scr.p;
+    p.ctl = h->knobs.no_r1 ? h->d_ctl.p : h->d_ctl_r1.p; p.work = h->d_work.p; p.llr_scr = h->d_llr_scr.p; p.c_scr = h->d_c_scr.p; p.hist_scr = h->d_hist_scr.p;
     p.flags = nullptr; p.cw_list = nullptr; p.cw_count = nullptr; p.n_dev = nullptr; p.tab_scr = nullptr; p.var_scr = nullptr;
 }
 

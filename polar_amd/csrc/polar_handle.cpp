@@ -186,6 +186,29 @@ int derive_tables(polar_code *h) {
         for (int i = 0; i < N; ++i)
             if (!h->frozen[i] && om[i] < 1e-3) { h->ctl[i] |= 0x100u; ++h->weak_leaves; }
     }
+    // Rate-1 blocks (the second control array, ctl_r1; `ctl` stays without the field and serves the knob no_r1): bits 9-10 of the
+    // control word of a leaf = log2 size (2 or 3, else 0) of the largest aligned block of
+    // unfrozen leaves that starts there, has no weak leaf, and whose decisions up to its last but one stay inside one
+    // history word (the flush after the 32nd unfrozen step then falls behind the block, never inside it). Leaf 4 of a marked
+    // octet carries its own quad. Only the list-of-32 units read the field (polar_scl_leaf.inc: a marked quad whose first leaf
+    // takes the fast path is finished in one step); every other kernel masks the word with 1, 0x7F << 1 and 0x100.
+    h->ctl_r1 = h->ctl;
+    if (h->n >= 4) {                                                // (as the rate-0 schedule: the layer of size 4 is a stored layer)
+        std::vector<int> tu((size_t)N + 1, 0);                      // unfrozen leaves before leaf i
+        for (int i = 0; i < N; ++i) tu[i + 1] = tu[i] + (h->frozen[i] ? 0 : 1);
+        auto rate1 = [&](int i0, int Z) {
+            if (i0 + Z > N) return false;
+            for (int i = i0; i < i0 + Z; ++i) {
+                if (h->frozen[i] || (h->ctl[i] & 0x100u)) return false;
+                if (i < i0 + Z - 1 && (tu[i] & 31) == 31) return false;
+            }
+            return true;
+        };
+        for (int i = 0; i < N; i += 4) {
+            if ((i & 7) == 0 && rate1(i, 8)) { h->ctl_r1[i] |= 3u << 9; h->ctl_r1[i + 4] |= 2u << 9; i += 4; continue; }
+            if (rate1(i, 4)) h->ctl_r1[i] |= 2u << 9;
+        }
+    }
     // CRC row i as a parity mask over unfrozen ranks, check bit included: crc_check passes iff
     // parity(history & mask_i) == 0 for every row (PolarCode.cpp:93-108)
     h->crc_mask.assign((size_t)crc * h->W, 0u);
@@ -226,6 +249,7 @@ int ensure_device(polar_code *h, DevGuard &dg) {
     int rc;
     if ((rc = upload(h->d_frozen, h->frozen))) return rc;
     if ((rc = upload(h->d_ctl, h->ctl))) return rc;
+    if ((rc = upload(h->d_ctl_r1, h->ctl_r1))) return rc;
     if ((rc = upload(h->d_sc_ops, h->sc_ops))) return rc;
     if ((rc = upload(h->d_sc_lat_ops, h->sc_lat_ops))) return rc;
     if ((rc = upload(h->d_order, h->order))) return rc;
@@ -258,6 +282,7 @@ int read_env_knobs(polar_code *h) {
     h->knobs.sc_no_fold = on("POLAR_SC_NO_FOLD");
     h->knobs.no_tables = on("POLAR_NO_TABLES");
     h->knobs.no_head = on("POLAR_NO_HEAD");
+    h->knobs.no_r1 = on("POLAR_NO_R1");
     h->knobs.no_rccl = on("POLAR_NO_RCCL");
     h->knobs.force_rccl = on("POLAR_FORCE_RCCL");
     return POLAR_OK;
@@ -359,7 +384,7 @@ void polar_destroy(polar_code_t *h) {
         if (h->dev_ready && hipGetDevice(&cur) == hipSuccess && cur != h->device) dg_.prev = cur;
     }
     if (h->dev_ready) (void)hipSetDevice(h->device);
-    h->d_frozen.release(); h->d_ctl.release(); h->d_crcm.release(); h->d_order.release(); h->d_info_rank.release();
+    h->d_frozen.release(); h->d_ctl.release(); h->d_ctl_r1.release(); h->d_crcm.release(); h->d_order.release(); h->d_info_rank.release();
     h->d_crc_mask.release(); h->d_tabs.release(); h->d_pre.release(); h->d_llr_scr.release(); h->d_c_scr.release(); h->d_hist_scr.release();
     h->d_in.release(); h->d_f32.release(); h->d_out.release(); h->d_bytes_a.release(); h->d_bytes_b.release();
     h->d_counter.release(); h->d_sel.release(); h->d_work.release();

@@ -234,6 +234,7 @@ struct polar_code {
     std::vector<uint32_t> crc_mask;  // [crc*W]
     std::vector<uint8_t> sched;      // [N] rate-0 block schedule for the kernel (0 / 2 / 3)
     std::vector<uint32_t> ctl;       // [N] frozen | sched << 1 | weak-unfrozen-leaf << 8
+    std::vector<uint32_t> ctl_r1;    // [N] the same | rate-1 block log2 size << 9 (derive_tables)
     int weak_leaves = 0;             // unfrozen leaves no construction for an ordinary channel would leave unfrozen (derive_tables)
     std::vector<uint32_t> sc_ops;    // schedule of the list-size-1 kernel (PolarScParams::ops)
     std::vector<uint32_t> sc_lat_ops;//   the same for its one-codeword-per-wave form: no folded F steps, mixed nodes of size 8 as ONE op (type 7)
@@ -244,7 +245,7 @@ struct polar_code {
     size_t lds_per_block = 0;        // hipDeviceAttributeMaxSharedMemoryPerBlock (160 KiB on gfx950): what the one-codeword-per-wave kernels are gated on
     DevBuf<uint8_t> d_frozen, d_crcm;
     DevBuf<uint16_t> d_order, d_info_rank;
-    DevBuf<uint32_t> d_crc_mask, d_ctl, d_sc_ops, d_sc_lat_ops, d_var_scr;
+    DevBuf<uint32_t> d_crc_mask, d_ctl, d_ctl_r1, d_sc_ops, d_sc_lat_ops, d_var_scr;
     DevBuf<double> d_tab_scr;
     DevBuf<unsigned long long> d_head_rec;   // two-phase list of 32: the hand-over records [B][rows][4] (polar_head_plan.h)
     int last_head_phi = 0;           //   hand-over leaf of the last decode_scl_llr call, 0 = one phase (polar_debug_get "head_phi")
@@ -288,6 +289,7 @@ struct polar_code {
         bool sc_no_fold = false;     // POLAR_SC_NO_FOLD: list size 1 decodes a permuted, converted copy (front pass)
         bool no_tables = false;      // POLAR_NO_TABLES: list of 17..32 without the layer-1/2 value tables
         bool no_head = false;        // POLAR_NO_HEAD: list of 17..32 in one phase (no 4-lane head, polar_head_plan.h)
+        bool no_r1 = false;          // POLAR_NO_R1: control words without the rate-1 block field (every leaf of such a block a loop step)
         long head_min_b = 0;         //   smallest batch that takes the head (0 = default: 16-codeword waves fill the device)
         bool no_fuse_front = false;  // (hook) exp-domain lists: separate conversion pass in front of the prefix kernel (the round-3 path)
         bool no_rccl = false;        // POLAR_NO_RCCL: multi-device counters summed on the host

@@ -32,9 +32,9 @@
 #include "polar_edom.h"
 
 #ifdef POLAR_PROFILE
-#define PROF_DECL u64 prof_acc[24] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}; u64 prof_t = __builtin_readcyclecounter();
+#define PROF_DECL u64 prof_acc[32] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}; u64 prof_t = __builtin_readcyclecounter();
 #define PROF(i) { u64 t_ = __builtin_readcyclecounter(); prof_acc[i] += t_ - prof_t; prof_t = t_; }
-#define PROF_OUT if (lane == 0 && p.pm_out) { for (int i_ = 0; i_ < 24; ++i_) atomicAdd((u64 *)p.pm_out + i_, prof_acc[i_]); }
+#define PROF_OUT if (lane == 0 && p.pm_out) { for (int i_ = 0; i_ < 32; ++i_) atomicAdd((u64 *)p.pm_out + i_, prof_acc[i_]); }
 #define PROF_CNT(i, v) { prof_acc[i] += (u64)(v); }
 // the few-path head: cycles of the leaf loop before the leaf the tool names in word 32 of its buffer -> [22], of the
 // whole loop -> [23] (tools/phase_profile.py prints the share). Like PROF_OUT, which adds its 24 words there, this takes p.pm_out for
@@ -43,7 +43,28 @@
 #define PROF_HEAD_DECL const int prof_head_phi = p.pm_out ? (int)((const u64 *)p.pm_out)[32] : 0; const u64 prof_head_t0 = prof_t; bool prof_head_open = prof_head_phi > 0;
 #define PROF_HEAD(phi_) if (prof_head_open && (phi_) >= prof_head_phi) { prof_acc[22] += __builtin_readcyclecounter() - prof_head_t0; prof_head_open = false; }
 #define PROF_HEAD_END prof_acc[23] += __builtin_readcyclecounter() - prof_head_t0;
+// rate-1 blocks: the host marks the aligned all-unfrozen blocks of 4 and 8 leaves in bits 9-10 of the control word of
+// their first leaf (rb = log2 size). Cycles of the loop iterations at positions 1 .. Z-1 of a marked block whose leaf 0 took the fast
+// path -> [24] (what finishing such a block in one step could remove at the most: the node arithmetic stays); such blocks -> [25],
+// marked blocks whose leaf 0 did not -> [26], leaves at positions 1 .. Z-1 of the former that left the fast path after all -> [27].
+// The continuation that finishes a quad in one step (units 2 and 6): its cycles -> [28], tried -> [29], committed -> [30].
+// PROF_R1_TOP stands right after PROF(0) (prof_t is the clock just read), PROF_R1_LEAF where an unfrozen leaf knows `fast`.
+// Word 33 of the tool's buffer != 0 keeps the continuation from starting (prof_r1_off): the marks stay, so [24] .. [27] measure the walk as
+// it is without it.
+#define PROF_R1_DECL int prof_r1_left = 0; bool prof_r1_open = false; u64 prof_r1_t0 = 0; const bool prof_r1_off = p.pm_out && ((const u64 *)p.pm_out)[33] != 0; (void)prof_r1_off;
+#define PROF_R1_TOP { if (prof_r1_open) { prof_acc[24] += prof_t - prof_r1_t0; prof_r1_open = false; } \
+                      if (prof_r1_left > 0) { prof_r1_t0 = prof_t; prof_r1_open = true; --prof_r1_left; } }
+#define PROF_R1_LEAF(ctl_, fast_) { const int rb_ = (int)((ctl_) >> 9) & 3; \
+                      if (prof_r1_open) { if (!(fast_)) prof_acc[27] += 1; } \
+                      else if (rb_) { if (fast_) { prof_acc[25] += 1; prof_r1_left = (1 << rb_) - 1; } else prof_acc[26] += 1; } }
+#define PROF_R1_COMMIT prof_r1_left = 0;
+#define PROF_R1_END if (prof_r1_open) { prof_acc[24] += __builtin_readcyclecounter() - prof_r1_t0; prof_r1_open = false; }
 #else
+#define PROF_R1_DECL constexpr bool prof_r1_off = false; (void)prof_r1_off;
+#define PROF_R1_TOP
+#define PROF_R1_LEAF(ctl_, fast_)
+#define PROF_R1_COMMIT
+#define PROF_R1_END
 #define PROF_HEAD_DECL
 #define PROF_HEAD(phi_)
 #define PROF_HEAD_END
@@ -134,6 +155,27 @@ __device__ __forceinline__ double ch_narrow(const double *row, size_t i, int fmt
 #ifndef POLAR_HEAD
 #define POLAR_HEAD 0
 #endif
+// Rate-1 quads finished in one step (polar_scl_leaf.inc): the list-of-32 units only (2 and 6); every other unit has
+// not one token of it. (Not in the margin build: that one measures every fork step by itself.)
+#if defined(POLAR_ED_TU) && (POLAR_ED_TU == 2 || POLAR_ED_TU == 6) && !defined(POLAR_MARGIN)
+#define POLAR_R1 1
+#else
+#define POLAR_R1 0
+#endif
+// The test library (POLAR_TEST_HOOKS, units 2 and 6 compiled again for it) counts the continuations of a launch: committed -> [0],
+// given up -> [1]; one atomic each per wave, after its work loop. The product carries no counter.
+#if POLAR_R1 && defined(POLAR_TEST_HOOKS)
+__device__ unsigned long long polar_r1_counts_dev[2];
+#define R1_CNT_DECL unsigned r1_cnt_c = 0, r1_cnt_d = 0;
+#define R1_CNT_COMMIT ++r1_cnt_c;
+#define R1_CNT_DISCARD ++r1_cnt_d;
+#define R1_CNT_OUT if (lane == 0) { atomicAdd(&polar_r1_counts_dev[0], (unsigned long long)r1_cnt_c); atomicAdd(&polar_r1_counts_dev[1], (unsigned long long)r1_cnt_d); }
+#else
+#define R1_CNT_DECL
+#define R1_CNT_COMMIT
+#define R1_CNT_DISCARD
+#define R1_CNT_OUT
+#endif
 template <int GS, int LDS_LOG, int PIPE, bool ED, int NL = 0, int LAT = 0>
 __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_llr_kernel(POLAR_KPARAMS p) {
     // ED: exp-domain node arithmetic (see f_node_e); the channel values at p.llr are then in stored form
@@ -214,6 +256,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
     // Work distribution: a wave's first group of codewords is its own index, every further one comes
     // from a device counter. Waves do not take equally long (per-wave time spreads by ~ +-15 %), and with
     // a static stride the launch ends when the unluckiest wave has finished ALL its groups.
+    R1_CNT_DECL
     for (long g0 = (long)wave_id * G; g0 < Bv;) {
         const long cwi = g0 + grp;                 // position in the work list
         const bool valid = (cwi < Bv);
@@ -346,6 +389,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
 
         PROF_DECL
         PROF_HEAD_DECL
+        PROF_R1_DECL
 #ifdef POLAR_MARGIN
         // development aid (tools/margin_profile.py): the smallest gap, over all pruning fork steps of this codeword, between
         // the worst surviving and the best discarded fork metric — what a lower-precision state would have to resolve
@@ -383,6 +427,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
 #endif
             PROF_HEAD(phi)
             PROF(0)
+            PROF_R1_TOP
             const uint32_t ctl = ctl_next;
             // recursivelyUpdateC (PolarCode.cpp:457-473) from the layer of size S upwards: X = column 1 of
             // that layer (the S bits just completed by a RIGHT child with node index ph)
@@ -474,12 +519,16 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
                     ctl_next = (uint32_t)__builtin_amdgcn_readlane((int)ctlv, nphi & 63);
                 } else ctl_next = ctlp[nphi < N ? nphi : 0];
             }
+#if POLAR_R1
+            bool r1_done = false;                  // (a marked rate-1 quad was finished in this step: polar_scl_leaf.inc)
+#endif
             const int lam_stop = n - zb;
             // recursivelyCalcLLR for this leaf, then the leaf itself (fragments of this function body: the kernel is one function, its
             // text is kept in three files)
 #include "polar_scl_visits.inc"
 #include "polar_scl_leaf.inc"
         }  // phi
+        PROF_R1_END
         PROF_HEAD_END
         PROF_OUT
 
@@ -537,6 +586,7 @@ __global__ __launch_bounds__(PIPE ? 64 : 256, PIPE ? 2 : OCC) void scl_decode_ll
             g0 += (long)nwaves * G;
         }
     }  // codeword groups
+    R1_CNT_OUT
 }
 
 // ------------------------------------------------------------------------------------------
@@ -953,7 +1003,17 @@ hipError_t polar_launch_decode_head_export(const PolarHeadParams &p, int grid, h
 }
 #elif POLAR_ED_TU == 6
 // phase B: the list of 32 from p.head_phi on (the instantiations launch_gs<32, true> picks in the default tuning)
+#ifdef POLAR_TEST_HOOKS
+static hipError_t r1_counts_zero(hipStream_t st) {
+    static const unsigned long long z[2] = {0, 0};
+    return hipMemcpyToSymbolAsync(HIP_SYMBOL(polar_r1_counts_dev), z, sizeof z, 0, hipMemcpyHostToDevice, st);
+}
+hipError_t polar_r1_counts_read_head(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(polar_r1_counts_dev), 2 * sizeof(unsigned long long)); }
+#endif
 hipError_t polar_launch_decode_head_import(const PolarHeadParams &p, int grid, hipStream_t st) {
+#ifdef POLAR_TEST_HOOKS
+    if (hipError_t e = r1_counts_zero(st)) return e;
+#endif
     if (!p.head_rec || p.L < 17 || p.L > 32 || p.head_phi <= 0 || p.head_phi >= p.N || grid < 4 || (grid & 3)) return hipErrorInvalidValue;
     const size_t lds = polar_decode_lds_bytes(3, 0);
 #ifndef POLAR_NO_FIXED_N
@@ -965,7 +1025,16 @@ hipError_t polar_launch_decode_head_import(const PolarHeadParams &p, int grid, h
     return hipGetLastError();
 }
 #elif POLAR_ED_TU == 2
+#ifdef POLAR_TEST_HOOKS
+hipError_t polar_r1_counts_read_ed32(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(polar_r1_counts_dev), 2 * sizeof(unsigned long long)); }
+#endif
 hipError_t polar_launch_decode_llr_ed1_gs32(const PolarDecodeParams &p, int lds_log, int pipe, int grid, hipStream_t st) {
+#ifdef POLAR_TEST_HOOKS
+    {
+        static const unsigned long long z[2] = {0, 0};
+        if (hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(polar_r1_counts_dev), z, sizeof z, 0, hipMemcpyHostToDevice, st)) return e;
+    }
+#endif
     return launch_gs<32, true>(p, lds_log, pipe, grid, st);
 }
 #elif POLAR_ED_TU == 1

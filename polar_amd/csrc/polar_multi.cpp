@@ -46,7 +46,7 @@ polar_code *copy_ctx(polar_code *h, int dev) {
     polar_code *c = new polar_code;
     c->n = h->n; c->N = h->N; c->K = h->K; c->crc = h->crc; c->eps = h->eps;
     c->frozen = h->frozen; c->order = h->order; c->bitrev = h->bitrev; c->crcm = h->crcm;
-    c->W = h->W; c->info_rank = h->info_rank; c->crc_mask = h->crc_mask; c->sched = h->sched; c->ctl = h->ctl;
+    c->W = h->W; c->info_rank = h->info_rank; c->crc_mask = h->crc_mask; c->sched = h->sched; c->ctl = h->ctl; c->ctl_r1 = h->ctl_r1;
     c->sc_ops = h->sc_ops; c->sc_lat_ops = h->sc_lat_ops; c->sc_fold = h->sc_fold; c->weak_leaves = h->weak_leaves;
     c->device = dev;
     c->waves_per_cu = h->waves_per_cu; c->lds_log = h->lds_log; c->pipe = h->pipe; c->prefix_on = h->prefix_on; c->mode = h->mode;

@@ -145,6 +145,7 @@
                     fast = wave_all((nact == 0) || (nact == L && gmax < bmin));
                 }
                 PROF_CNT(8, 1)
+                PROF_R1_LEAF(ctl, fast)
                 PROF(16)
                 if (fast) {      // (marking this likely — the ranking path out of line — measured -0.5 %)
                     PROF_CNT(9, 1)
@@ -161,6 +162,98 @@
                         hword |= ubit << (t & 31);
                     }
                     PROF(17)
+#if POLAR_R1
+                    if constexpr (ED && !LAT && GS == 32) {
+                    if ((ctl & 0x600u) && !prof_r1_off) {
+                        // ---- rate-1 quad continuation. This leaf is the first of an aligned block of four unfrozen leaves
+                        // (host mark: no weak leaf, no history flush before the block's last leaf) and took the fast path: the
+                        // list is full, nobody was killed or cloned, and the f-chain that came down to this leaf wrote the layers of
+                        // size 4 and 2 into THIS lane's own slots. If the three leaves that follow take the fast path too, every
+                        // path just takes the bit its leaf favours, and the four steps are one: the leaf values of positions 1..3
+                        // are computed here from those two layers, the fast-path test is run for each of them in order on
+                        // temporaries, and only if all three pass (in both lane groups) is anything committed. Otherwise nothing
+                        // was written and the loop goes on at phi + 1 as ever (gacc may have seen the f-node of leaf 2 early: the minimum the walk
+                        // takes again there, or — when the block is given up over a value of magnitude 1.0, whose g-nodes above got a
+                        // bit the walk would not use — one the walk never takes: an extra minimum only makes the fallback flag more
+                        // likely, never less).
+                        //
+                        // The g-nodes are called with u = s(a) ^ s(b), the sign bits of their own operands, instead of the
+                        // partial sums of the decisions — the same g_node_e call, rare arm included, because on this path the two
+                        // agree: a leaf decides neg = signbit(v) && |v| != 1, and signbit(f(a, b)) = s(a) ^ s(b) (ed_with_sign in
+                        // f_node_e_acc), so with |leaf0| != 1 the left leaf of the pair (y0, y1) returns u0 = s(y0) ^ s(y1); then
+                        // g(y0, y1, u0) flips y0 onto the sign of y1, takes its "same sign" arm, whose result carries s(y1) (also
+                        // through g_node_e_rare: a sum of two values of one sign), and with |leaf1| != 1 decides u1 = s(y1). The
+                        // pair hands (u0 ^ u1, u1) = (s(y0), s(y1)) = (s(x0) ^ s(x2), s(x1) ^ s(x3)) to the layer of size 2: the very
+                        // bits the g-visit of leaf 2 is given for (x0, x2) and (x1, x3). The second pair repeats the first. A value
+                        // of magnitude exactly 1.0 (LLR 0) with its sign bit set breaks the first step — it decides 0 —, so a block
+                        // in which any of the four leaf values of any active lane has |v| == 1.0 is left to the loop.
+                        PROF_CNT(29, 1)
+                        // (the control word of the leaf behind the quad, should it be finished here: asked for now, needed at the commit —
+                        // loaded at the top of the step it would be one more scalar held across the layer visits)
+                        const uint32_t ctl_r1 = ctlp[phi + 4 < N ? phi + 4 : 0];
+                        const double *yq = lds_llr + (size_t)1 * 64 + lane, *xq = lds_llr + (size_t)3 * 64 + lane;      // layers of size 2, 4
+                        double lf[3] = {0.0, 0.0, 0.0};
+                        if (active) {
+                            const double y0 = yq[0], y1 = yq[64], x0 = xq[0], x1 = xq[64], x2 = xq[128], x3 = xq[192];
+                            auto gss = [&](double a_, double b_) { return g_node_e(a_, b_, (unsigned)(__double2hiint(a_) ^ __double2hiint(b_)), tb); };
+                            const double z0 = gss(x0, x2), z1 = gss(x1, x3);
+                            lf[0] = gss(y0, y1);
+                            lf[1] = FN(z0, z1);
+                            lf[2] = gss(z0, z1);
+                        }
+                        // the three fast-path tests in leaf order, on temporaries: metric of the good forks so far (pmq), the sufficient
+                        // test on the high words alone (see the step above). Where high words collide or the test fails the block is
+                        // left to the loop, which runs the exact reductions itself: giving up is always exact.
+                        double pmq = pm;
+                        u64 m_lt = ~0ull, m_one = __builtin_amdgcn_fcmp(fabs(leaf), 1.0, 1);       // OEQ
+                        uint32_t uq = 0;
+#pragma unroll
+                        for (int i_ = 0; i_ < 3; ++i_) {
+                            bool ng1; double al1, sn1, sp1;
+                            leaf_terms<ED>(lf[i_], active, actw, tb, ng1, al1, sn1, sp1);
+                            const double gq = pmq + sn1, bq = (pmq + al1) * 0.99999999999909050530;
+                            unsigned gh_ = active ? (unsigned)__double2hiint(gq) : 0u, bh_ = active ? (unsigned)__double2hiint(bq) : 0xFFFFFFFFu;
+                            group_max_min_u32<GS>(gh_, bh_);
+                            m_lt &= __builtin_amdgcn_uicmp(gh_, bh_, 36);                          // ULT
+                            m_one |= __builtin_amdgcn_fcmp(fabs(lf[i_]), 1.0, 1);
+                            pmq = gq;
+                            uq |= (ng1 ? 1u : 0u) << i_;
+                        }
+                        const u64 m_okq = __builtin_amdgcn_sicmp(nact, 0, 32) | (__builtin_amdgcn_sicmp(nact, L, 32) & m_lt);
+                        const bool pass = ((m_okq | ~group_result_rows<GS>()) == ~0ull) && (m_one & actw) == 0;
+                        if (pass) {
+                            PROF_CNT(30, 1)
+                            PROF_CNT(8, 3)
+                            PROF_CNT(9, 3)
+                            PROF_R1_COMMIT
+                            const uint32_t u1 = uq & 1u, u2 = (uq >> 1) & 1u, u3 = uq >> 2;
+                            if (active) {
+                                pm = pmq;
+                                hword |= (u1 << ((t + 1) & 31)) | (u2 << ((t + 2) & 31)) | (u3 << ((t + 3) & 31));
+                            }
+                            // the quad's partial sums, as the four calls of the leaf's own update would have left them: after leaf 1
+                            // the layer of size 2 holds (u0 ^ u1, u1), after leaf 3 the layer of size 4 gets that pair XOR (u2 ^ u3, u3)
+                            // followed by (u2 ^ u3, u3); from there exactly as the rate-0 block hands over its zeros
+                            const uint32_t X = (ubit ^ u1 ^ u2 ^ u3) | ((u1 ^ u3) << 1) | ((u2 ^ u3) << 2) | (u3 << 3);
+                            const int nu = phi >> 2;
+                            if ((nu & 1) == 0) {
+                                if (active) clsmall = (clsmall & ~(0xFull << 4)) | ((u64)X << 4);
+                            } else {
+                                update_c(4, X, nu);
+                            }
+                            wave_mem_fence();
+                            t += 3;
+                            phi += 3;
+                            ctl_next = ctl_r1;
+                            r1_done = true;
+                            R1_CNT_COMMIT
+                        } else {
+                            R1_CNT_DISCARD
+                        }
+                        PROF(28)
+                    }
+                    }
+#endif
                 } else {
                 double pf0 = __builtin_nan(""), pf1 = __builtin_nan("");
                 if (active) {
@@ -434,6 +527,11 @@
 
             PROF(frozen ? 5 : 6)
             // ---------------- partial sums ----------------
+#if POLAR_R1
+            if (r1_done) {
+                // (a rate-1 quad finished in one step has handed its partial sums over itself)
+            } else
+#endif
             if ((phi & 1) == 0) {
                 // left leaf: column 0 of C_n (size 1) lives at bit 1 of clsmall
                 if (active) clsmall = (clsmall & ~2ull) | ((u64)ubit << 1);

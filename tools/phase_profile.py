@@ -2,7 +2,11 @@
 """Per-phase cycle breakdown of scl_decode_llr_kernel (instrumented build, -DPOLAR_PROFILE).
 Run on the GPU box: python tools/phase_profile.py [L] [batch] [wpc] [lds_log]
 HEAD_PHI=<leaf> (default 432, the headline code's hand-over leaf; 0 = off) also prints the share of the leaf loop's cycles spent
-before that leaf: the few-path head of DESIGN.md §4."""
+before that leaf: the few-path head of DESIGN.md §4.
+The rate-1 block lines give the cycles of the loop iterations at positions 1 .. Z-1 of the host-marked all-unfrozen
+blocks of 4 and 8 leaves whose first leaf took the fast path: the most that finishing such a block in one step could remove.
+R1_OFF=1 keeps the list-of-32 kernels from finishing marked quads in one step (the marks stay: the lines above then describe the walk
+without the continuation); otherwise its own cycles and its tried / committed counts are printed."""
 import ctypes as C
 import os
 import sys
@@ -30,22 +34,29 @@ torch.cuda.synchronize()
 prof.zero_()
 head_phi = int(os.environ.get("HEAD_PHI", "432"))
 prof[32] = head_phi                                       # (read by the kernel: PROF_HEAD_DECL)
+prof[33] = 1 if os.environ.get("R1_OFF") else 0          # (PROF_R1_DECL)
 torch.cuda.synchronize()
 import time
 t = time.perf_counter()
 g.decode_scl_llr_dev(llr.data_ptr(), B, L, out.data_ptr(), prof.data_ptr())
 torch.cuda.synchronize()
 dt = time.perf_counter() - t
-a = prof[:24].cpu().numpy().astype(float)
+a = prof[:32].cpu().numpy().astype(float)
 names = ["loop ovh", "layer S>SL g (HBM)", "layer S>SL f (HBM)", "layer 4<=S<=SL (LDS)", "layer S<4", "leaf frozen / rate-0 block", "leaf unfrozen (rest: flush etc.)", "partial sums", "unf: DPP reductions+decision", "unf: competitive-bad loop", "unf: stack/srcof", "unf: clone shuffles+update", "-", "unf: setup+goods rank loop", "unf: wait for leaf (ballot)", "unf: softplus+bounds"]
 print(f"L={L} B={B} time {dt*1e3:.2f} ms -> {B/dt:.0f} cw/s")
-cyc = a[:8].sum() + a[16:22].sum()                        # ([22], [23]: the head split below, not phases)
+cyc = a[:8].sum() + a[16:22].sum() + a[28]                # ([22], [23]: the head split below, not phases; [28]: the quad continuation)
 nwd = B / (64 // max(1, 1 << (L - 1).bit_length()))      # wave-decodes
 if os.environ.get("LATPROF"):                             # the one-codeword-per-wave kernels: a wave-decode is a codeword
     nwd = B
 print(f"  cycles per wave-decode: {cyc/nwd:.0f}")
 if head_phi and a[23] > 0:
     print(f"  leaves before {head_phi} (few-path head): {100*a[22]/a[23]:.2f}% of the leaf loop  {a[22]/nwd:10.0f} of {a[23]/nwd:.0f} cycles/wave-decode")
+if a[25] + a[26] > 0 and a[23] > 0:
+    print(f"  rate-1 blocks (marked, per wave) {a[25] + a[26]:.0f}: leaf 0 on the fast path {100*a[25]/(a[25] + a[26]):.1f}%; "
+          f"later leaves of those that left it {a[27]:.0f}")
+    print(f"  iterations 1..Z-1 of the blocks that started fast: {100*a[24]/a[23]:.2f}% of the leaf loop  {a[24]/nwd:10.0f} of {a[23]/nwd:.0f} cycles/wave-decode")
+if a[29] > 0:
+    print(f"  quad continuation (per wave): tried {a[29]:.0f}, committed {100*a[30]/a[29]:.1f}%; {100*a[28]/cyc:.1f}% of the cycles  {a[28]/nwd:10.0f} cycles/wave-decode")
 for nm, v in zip(names[:8], a[:8]):
     print(f"  {nm:34s} {100*v/cyc:5.1f}%  {v/nwd:10.0f} cycles/wave-decode")
 sub = ["unf: leaf wait + softplus + DPP bounds", "unf: fast path commit", "unf: goods rank loop", "unf: competitive-bad loop",
