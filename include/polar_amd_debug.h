@@ -61,7 +61,10 @@ long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap);
 /* The per-leaf control words as uploaded (marked != 0: with the rate-1 block field in bits 9-10, else the plain array the knob
  * "no_r1" selects): copies min(N, cap) words, returns N; below 0: -(1 + hipError_t). Both libraries. polar_debug_get
  * "r1_committed" / "r1_discarded" (test build only): the rate-1 quad continuations the last list-of-32 launch of the handle's
- * last call finished in one step / gave up, counted per wave. */
+ * last call finished in one step / gave up, counted per wave: "committed" = quads finished whose own first leaf passed its test (a
+ * chained second quad of an octet included), "discarded" = continuations tried in the loop after a fast first leaf and given up.
+ * "r1_rank_tried" / "r1_rank_committed": continuations entered after a first leaf that took the ranking path; "r1_chain_tried" /
+ * "r1_chain_committed": second quads of marked octets tried / finished in the step that finished the first. */
 long polar_debug_ctl_words(polar_code_t *h, uint32_t *words, long cap, int marked);
 /* number of ncclCommInitAll calls made by this library so far (the communicators of a device list are cached on the handle) */
 int polar_debug_comm_inits(void);

@@ -46,7 +46,7 @@ LIB_TEST = os.path.join(HERE, "libpolar_amd_test.so")
 # what POLAR_DEFS may name: instrumentation (measures, does not decode), trimmed development builds (fewer instantiations),
 # and the few A/B switches still open (same bits either way)
 KNOWN_DEFS = {"POLAR_MARGIN", "POLAR_SLOTHIST", "SCLAT_PROF", "POLAR_DEV_GS32", "POLAR_DEV_ONE", "POLAR_NO_FIXED_N",
-              "POLAR_NO_GUARD_INT", "POLAR_NO_COLD_HINTS", "OCC", "ED_NR"}
+              "POLAR_NO_GUARD_INT", "POLAR_NO_COLD_HINTS", "OCC", "ED_NR", "POLAR_R1_RANK", "POLAR_R1_CHAIN"}
 ARCH = os.environ.get("POLAR_ARCH", "gfx950")      # (A/B: e.g. gfx950:xnack-)
 _flags_ok = {}
 

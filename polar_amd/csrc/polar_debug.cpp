@@ -99,12 +99,17 @@ long polar_debug_get(const polar_code_t *h, const char *key) {
         }
         return bad;
     }
-    if (s == "r1_committed" || s == "r1_discarded") {
+    if (s.compare(0, 3, "r1_") == 0) {
         // rate-1 quad continuations of the last list-of-32 launch (the unit the handle's last call took: the two-phase import or
-        // the single-phase kernel): finished in one step / given up. The caller has synchronised the call's stream.
-        unsigned long long c[2] = {0, 0};
-        if ((h->last_head_phi ? polar_r1_counts_read_head(c) : polar_r1_counts_read_ed32(c)) != hipSuccess) return -2;
-        return (long)c[s == "r1_discarded" ? 1 : 0];
+        // the single-phase kernel): finished in one step / given up; tried / finished after a first leaf that took the ranking
+        // path; second quads of octets tried / finished in the step of the first. The caller has synchronised the call's stream.
+        static const char *const names[6] = {"r1_committed", "r1_discarded", "r1_rank_tried", "r1_rank_committed", "r1_chain_tried", "r1_chain_committed"};
+        for (int i = 0; i < 6; ++i) {
+            if (s != names[i]) continue;
+            unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
+            if ((h->last_head_phi ? polar_r1_counts_read_head(c) : polar_r1_counts_read_ed32(c)) != hipSuccess) return -2;
+            return (long)c[i];
+        }
     }
 #endif
     if (s == "last_rounds") return h->last_rounds;

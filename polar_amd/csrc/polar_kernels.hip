@@ -32,9 +32,10 @@
 #include "polar_edom.h"
 
 #ifdef POLAR_PROFILE
-#define PROF_DECL u64 prof_acc[32] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}; u64 prof_t = __builtin_readcyclecounter();
+// (words 32 and 33 of the tool's buffer are its inputs: the accumulators from [32] on land two words further up)
+#define PROF_DECL u64 prof_acc[40] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}; u64 prof_t = __builtin_readcyclecounter();
 #define PROF(i) { u64 t_ = __builtin_readcyclecounter(); prof_acc[i] += t_ - prof_t; prof_t = t_; }
-#define PROF_OUT if (lane == 0 && p.pm_out) { for (int i_ = 0; i_ < 32; ++i_) atomicAdd((u64 *)p.pm_out + i_, prof_acc[i_]); }
+#define PROF_OUT if (lane == 0 && p.pm_out) { for (int i_ = 0; i_ < 40; ++i_) atomicAdd((u64 *)p.pm_out + (i_ < 32 ? i_ : i_ + 2), prof_acc[i_]); }
 #define PROF_CNT(i, v) { prof_acc[i] += (u64)(v); }
 // the few-path head: cycles of the leaf loop before the leaf the tool names in word 32 of its buffer -> [22], of the
 // whole loop -> [23] (tools/phase_profile.py prints the share). Like PROF_OUT, which adds its 24 words there, this takes p.pm_out for
@@ -51,19 +52,32 @@
 // PROF_R1_TOP stands right after PROF(0) (prof_t is the clock just read), PROF_R1_LEAF where an unfrozen leaf knows `fast`.
 // Word 33 of the tool's buffer != 0 keeps the continuation from starting (prof_r1_off): the marks stay, so [24] .. [27] measure the walk as
 // it is without it.
-#define PROF_R1_DECL int prof_r1_left = 0; bool prof_r1_open = false; u64 prof_r1_t0 = 0; const bool prof_r1_off = p.pm_out && ((const u64 *)p.pm_out)[33] != 0; (void)prof_r1_off;
-#define PROF_R1_TOP { if (prof_r1_open) { prof_acc[24] += prof_t - prof_r1_t0; prof_r1_open = false; } \
+// Sequel ("octets in one step"): cycles of the loop iterations at positions 1 .. 3 of a marked quad whose leaf 0 took the
+// ranking path with the list full -> [32], such quads -> [33]; cycles of the whole leaf-4 iteration (layer visits and partial sums included)
+// of a marked octet whose first quad was committed and whose second was not chained -> [34], such iterations -> [35]. The continuation
+// entered after a ranking step: tried -> [36], committed -> [37]; the second quad of an octet chained in the same step: tried -> [38],
+// committed -> [39]. Word 33 of the tool's buffer: bit 0 keeps every continuation from starting, bit 1 the entry after a ranking step,
+// bit 2 the chain (so [32] .. [35] can measure the walk without them).
+#define PROF_R1_DECL int prof_r1_left = 0, prof_r1_slot = 24; bool prof_r1_open = false; u64 prof_r1_t0 = 0; \
+                     const unsigned prof_r1_sw = p.pm_out ? (unsigned)((const u64 *)p.pm_out)[33] : 0u; \
+                     const bool prof_r1_off = (prof_r1_sw & 1u) != 0, prof_rank_off = (prof_r1_sw & 2u) != 0, prof_chain_off = (prof_r1_sw & 4u) != 0; \
+                     (void)prof_r1_off; (void)prof_rank_off; (void)prof_chain_off;
+#define PROF_R1_ADD(d_) { if (prof_r1_slot == 24) prof_acc[24] += (d_); else if (prof_r1_slot == 32) prof_acc[32] += (d_); else prof_acc[34] += (d_); }
+#define PROF_R1_TOP { if (prof_r1_open) { PROF_R1_ADD(prof_t - prof_r1_t0) prof_r1_open = false; } \
                       if (prof_r1_left > 0) { prof_r1_t0 = prof_t; prof_r1_open = true; --prof_r1_left; } }
-#define PROF_R1_LEAF(ctl_, fast_) { const int rb_ = (int)((ctl_) >> 9) & 3; \
-                      if (prof_r1_open) { if (!(fast_)) prof_acc[27] += 1; } \
-                      else if (rb_) { if (fast_) { prof_acc[25] += 1; prof_r1_left = (1 << rb_) - 1; } else prof_acc[26] += 1; } }
+#define PROF_R1_LEAF(ctl_, fast_, full_) { const int rb_ = (int)((ctl_) >> 9) & 3; \
+                      if (prof_r1_open) { if (!(fast_) && prof_r1_slot == 24) prof_acc[27] += 1; } \
+                      else if (rb_) { if (fast_) { prof_acc[25] += 1; prof_r1_left = (1 << rb_) - 1; prof_r1_slot = 24; } \
+                                      else { prof_acc[26] += 1; if (full_) { prof_acc[33] += 1; prof_r1_left = 3; prof_r1_slot = 32; } } } }
 #define PROF_R1_COMMIT prof_r1_left = 0;
-#define PROF_R1_END if (prof_r1_open) { prof_acc[24] += __builtin_readcyclecounter() - prof_r1_t0; prof_r1_open = false; }
+#define PROF_R1_OCTET(open_) if (open_) { prof_acc[35] += 1; prof_r1_left = 1; prof_r1_slot = 34; }
+#define PROF_R1_END if (prof_r1_open) { PROF_R1_ADD(__builtin_readcyclecounter() - prof_r1_t0) prof_r1_open = false; }
 #else
-#define PROF_R1_DECL constexpr bool prof_r1_off = false; (void)prof_r1_off;
+#define PROF_R1_DECL constexpr bool prof_r1_off = false, prof_rank_off = false, prof_chain_off = false; (void)prof_r1_off; (void)prof_rank_off; (void)prof_chain_off;
 #define PROF_R1_TOP
-#define PROF_R1_LEAF(ctl_, fast_)
+#define PROF_R1_LEAF(ctl_, fast_, full_)
 #define PROF_R1_COMMIT
+#define PROF_R1_OCTET(open_)
 #define PROF_R1_END
 #define PROF_HEAD_DECL
 #define PROF_HEAD(phi_)
@@ -162,18 +176,27 @@ __device__ __forceinline__ double ch_narrow(const double *row, size_t i, int fmt
 #else
 #define POLAR_R1 0
 #endif
-// The test library (POLAR_TEST_HOOKS, units 2 and 6 compiled again for it) counts the continuations of a launch: committed -> [0],
-// given up -> [1]; one atomic each per wave, after its work loop. The product carries no counter.
+// Its two sequels, each with a build-time switch of its own (A/B: POLAR_DEFS="POLAR_R1_RANK=0" / "POLAR_R1_CHAIN=0"): the continuation
+// also after a first leaf that took the ranking path with the list full, and the second quad of a marked octet in the same step.
+#ifndef POLAR_R1_RANK
+#define POLAR_R1_RANK 1
+#endif
+#ifndef POLAR_R1_CHAIN
+#define POLAR_R1_CHAIN 1
+#endif
+// The test library (POLAR_TEST_HOOKS, units 2 and 6 compiled again for it) counts the continuations of a launch: quads finished whose
+// own first leaf passed its test (after a fast first leaf in the loop, or as the chained second quad of an octet) -> [0]; tried in the
+// loop after a fast first leaf and given up -> [1]; tried / committed after a first leaf that took the ranking path -> [2] / [3];
+// second quads of octets tried / committed in the step of the first -> [4] / [5]. One atomic each per wave, after its work loop. The
+// product carries no counter.
 #if POLAR_R1 && defined(POLAR_TEST_HOOKS)
-__device__ unsigned long long polar_r1_counts_dev[2];
-#define R1_CNT_DECL unsigned r1_cnt_c = 0, r1_cnt_d = 0;
-#define R1_CNT_COMMIT ++r1_cnt_c;
-#define R1_CNT_DISCARD ++r1_cnt_d;
-#define R1_CNT_OUT if (lane == 0) { atomicAdd(&polar_r1_counts_dev[0], (unsigned long long)r1_cnt_c); atomicAdd(&polar_r1_counts_dev[1], (unsigned long long)r1_cnt_d); }
+__device__ unsigned long long polar_r1_counts_dev[6];
+#define R1_CNT_DECL unsigned r1_cnt[6] = {0, 0, 0, 0, 0, 0};
+#define R1_CNT(i_) ++r1_cnt[i_];
+#define R1_CNT_OUT if (lane == 0) { for (int i_ = 0; i_ < 6; ++i_) atomicAdd(&polar_r1_counts_dev[i_], (unsigned long long)r1_cnt[i_]); }
 #else
 #define R1_CNT_DECL
-#define R1_CNT_COMMIT
-#define R1_CNT_DISCARD
+#define R1_CNT(i_)
 #define R1_CNT_OUT
 #endif
 template <int GS, int LDS_LOG, int PIPE, bool ED, int NL = 0, int LAT = 0>
@@ -1005,10 +1028,10 @@ hipError_t polar_launch_decode_head_export(const PolarHeadParams &p, int grid, h
 // phase B: the list of 32 from p.head_phi on (the instantiations launch_gs<32, true> picks in the default tuning)
 #ifdef POLAR_TEST_HOOKS
 static hipError_t r1_counts_zero(hipStream_t st) {
-    static const unsigned long long z[2] = {0, 0};
+    static const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
     return hipMemcpyToSymbolAsync(HIP_SYMBOL(polar_r1_counts_dev), z, sizeof z, 0, hipMemcpyHostToDevice, st);
 }
-hipError_t polar_r1_counts_read_head(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(polar_r1_counts_dev), 2 * sizeof(unsigned long long)); }
+hipError_t polar_r1_counts_read_head(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(polar_r1_counts_dev), 6 * sizeof(unsigned long long)); }
 #endif
 hipError_t polar_launch_decode_head_import(const PolarHeadParams &p, int grid, hipStream_t st) {
 #ifdef POLAR_TEST_HOOKS
@@ -1026,12 +1049,12 @@ hipError_t polar_launch_decode_head_import(const PolarHeadParams &p, int grid, h
 }
 #elif POLAR_ED_TU == 2
 #ifdef POLAR_TEST_HOOKS
-hipError_t polar_r1_counts_read_ed32(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(polar_r1_counts_dev), 2 * sizeof(unsigned long long)); }
+hipError_t polar_r1_counts_read_ed32(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(polar_r1_counts_dev), 6 * sizeof(unsigned long long)); }
 #endif
 hipError_t polar_launch_decode_llr_ed1_gs32(const PolarDecodeParams &p, int lds_log, int pipe, int grid, hipStream_t st) {
 #ifdef POLAR_TEST_HOOKS
     {
-        static const unsigned long long z[2] = {0, 0};
+        static const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
         if (hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(polar_r1_counts_dev), z, sizeof z, 0, hipMemcpyHostToDevice, st)) return e;
     }
 #endif

@@ -145,7 +145,7 @@
                     fast = wave_all((nact == 0) || (nact == L && gmax < bmin));
                 }
                 PROF_CNT(8, 1)
-                PROF_R1_LEAF(ctl, fast)
+                PROF_R1_LEAF(ctl, fast, ((__builtin_amdgcn_sicmp(nact, 0, 32) | __builtin_amdgcn_sicmp(nact, L, 32)) == ~0ull))
                 PROF(16)
                 if (fast) {      // (marking this likely — the ranking path out of line — measured -0.5 %)
                     PROF_CNT(9, 1)
@@ -162,98 +162,6 @@
                         hword |= ubit << (t & 31);
                     }
                     PROF(17)
-#if POLAR_R1
-                    if constexpr (ED && !LAT && GS == 32) {
-                    if ((ctl & 0x600u) && !prof_r1_off) {
-                        // ---- rate-1 quad continuation. This leaf is the first of an aligned block of four unfrozen leaves
-                        // (host mark: no weak leaf, no history flush before the block's last leaf) and took the fast path: the
-                        // list is full, nobody was killed or cloned, and the f-chain that came down to this leaf wrote the layers of
-                        // size 4 and 2 into THIS lane's own slots. If the three leaves that follow take the fast path too, every
-                        // path just takes the bit its leaf favours, and the four steps are one: the leaf values of positions 1..3
-                        // are computed here from those two layers, the fast-path test is run for each of them in order on
-                        // temporaries, and only if all three pass (in both lane groups) is anything committed. Otherwise nothing
-                        // was written and the loop goes on at phi + 1 as ever (gacc may have seen the f-node of leaf 2 early: the minimum the walk
-                        // takes again there, or — when the block is given up over a value of magnitude 1.0, whose g-nodes above got a
-                        // bit the walk would not use — one the walk never takes: an extra minimum only makes the fallback flag more
-                        // likely, never less).
-                        //
-                        // The g-nodes are called with u = s(a) ^ s(b), the sign bits of their own operands, instead of the
-                        // partial sums of the decisions — the same g_node_e call, rare arm included, because on this path the two
-                        // agree: a leaf decides neg = signbit(v) && |v| != 1, and signbit(f(a, b)) = s(a) ^ s(b) (ed_with_sign in
-                        // f_node_e_acc), so with |leaf0| != 1 the left leaf of the pair (y0, y1) returns u0 = s(y0) ^ s(y1); then
-                        // g(y0, y1, u0) flips y0 onto the sign of y1, takes its "same sign" arm, whose result carries s(y1) (also
-                        // through g_node_e_rare: a sum of two values of one sign), and with |leaf1| != 1 decides u1 = s(y1). The
-                        // pair hands (u0 ^ u1, u1) = (s(y0), s(y1)) = (s(x0) ^ s(x2), s(x1) ^ s(x3)) to the layer of size 2: the very
-                        // bits the g-visit of leaf 2 is given for (x0, x2) and (x1, x3). The second pair repeats the first. A value
-                        // of magnitude exactly 1.0 (LLR 0) with its sign bit set breaks the first step — it decides 0 —, so a block
-                        // in which any of the four leaf values of any active lane has |v| == 1.0 is left to the loop.
-                        PROF_CNT(29, 1)
-                        // (the control word of the leaf behind the quad, should it be finished here: asked for now, needed at the commit —
-                        // loaded at the top of the step it would be one more scalar held across the layer visits)
-                        const uint32_t ctl_r1 = ctlp[phi + 4 < N ? phi + 4 : 0];
-                        const double *yq = lds_llr + (size_t)1 * 64 + lane, *xq = lds_llr + (size_t)3 * 64 + lane;      // layers of size 2, 4
-                        double lf[3] = {0.0, 0.0, 0.0};
-                        if (active) {
-                            const double y0 = yq[0], y1 = yq[64], x0 = xq[0], x1 = xq[64], x2 = xq[128], x3 = xq[192];
-                            auto gss = [&](double a_, double b_) { return g_node_e(a_, b_, (unsigned)(__double2hiint(a_) ^ __double2hiint(b_)), tb); };
-                            const double z0 = gss(x0, x2), z1 = gss(x1, x3);
-                            lf[0] = gss(y0, y1);
-                            lf[1] = FN(z0, z1);
-                            lf[2] = gss(z0, z1);
-                        }
-                        // the three fast-path tests in leaf order, on temporaries: metric of the good forks so far (pmq), the sufficient
-                        // test on the high words alone (see the step above). Where high words collide or the test fails the block is
-                        // left to the loop, which runs the exact reductions itself: giving up is always exact.
-                        double pmq = pm;
-                        u64 m_lt = ~0ull, m_one = __builtin_amdgcn_fcmp(fabs(leaf), 1.0, 1);       // OEQ
-                        uint32_t uq = 0;
-#pragma unroll
-                        for (int i_ = 0; i_ < 3; ++i_) {
-                            bool ng1; double al1, sn1, sp1;
-                            leaf_terms<ED>(lf[i_], active, actw, tb, ng1, al1, sn1, sp1);
-                            const double gq = pmq + sn1, bq = (pmq + al1) * 0.99999999999909050530;
-                            unsigned gh_ = active ? (unsigned)__double2hiint(gq) : 0u, bh_ = active ? (unsigned)__double2hiint(bq) : 0xFFFFFFFFu;
-                            group_max_min_u32<GS>(gh_, bh_);
-                            m_lt &= __builtin_amdgcn_uicmp(gh_, bh_, 36);                          // ULT
-                            m_one |= __builtin_amdgcn_fcmp(fabs(lf[i_]), 1.0, 1);
-                            pmq = gq;
-                            uq |= (ng1 ? 1u : 0u) << i_;
-                        }
-                        const u64 m_okq = __builtin_amdgcn_sicmp(nact, 0, 32) | (__builtin_amdgcn_sicmp(nact, L, 32) & m_lt);
-                        const bool pass = ((m_okq | ~group_result_rows<GS>()) == ~0ull) && (m_one & actw) == 0;
-                        if (pass) {
-                            PROF_CNT(30, 1)
-                            PROF_CNT(8, 3)
-                            PROF_CNT(9, 3)
-                            PROF_R1_COMMIT
-                            const uint32_t u1 = uq & 1u, u2 = (uq >> 1) & 1u, u3 = uq >> 2;
-                            if (active) {
-                                pm = pmq;
-                                hword |= (u1 << ((t + 1) & 31)) | (u2 << ((t + 2) & 31)) | (u3 << ((t + 3) & 31));
-                            }
-                            // the quad's partial sums, as the four calls of the leaf's own update would have left them: after leaf 1
-                            // the layer of size 2 holds (u0 ^ u1, u1), after leaf 3 the layer of size 4 gets that pair XOR (u2 ^ u3, u3)
-                            // followed by (u2 ^ u3, u3); from there exactly as the rate-0 block hands over its zeros
-                            const uint32_t X = (ubit ^ u1 ^ u2 ^ u3) | ((u1 ^ u3) << 1) | ((u2 ^ u3) << 2) | (u3 << 3);
-                            const int nu = phi >> 2;
-                            if ((nu & 1) == 0) {
-                                if (active) clsmall = (clsmall & ~(0xFull << 4)) | ((u64)X << 4);
-                            } else {
-                                update_c(4, X, nu);
-                            }
-                            wave_mem_fence();
-                            t += 3;
-                            phi += 3;
-                            ctl_next = ctl_r1;
-                            r1_done = true;
-                            R1_CNT_COMMIT
-                        } else {
-                            R1_CNT_DISCARD
-                        }
-                        PROF(28)
-                    }
-                    }
-#endif
                 } else {
                 double pf0 = __builtin_nan(""), pf1 = __builtin_nan("");
                 if (active) {
@@ -508,6 +416,172 @@
                 }
                 PROF(21)
                 }   // general path
+#if POLAR_R1
+                if constexpr (ED && !LAT && GS == 32) {
+                bool r1_go = false;
+                if ((ctl & 0x600u) && !prof_r1_off) {
+                    r1_go = fast;
+#if POLAR_R1_RANK
+                    // (after a ranking step: the list was full in every group that has paths, so it still is)
+                    if (!fast && !prof_rank_off) r1_go = ((__builtin_amdgcn_sicmp(nact, 0, 32) | __builtin_amdgcn_sicmp(nact, L, 32)) == ~0ull);   // EQ, EQ
+#endif
+                }
+                if (r1_go) {
+                    // ---- rate-1 quad continuation. This leaf is the first of an aligned block of four unfrozen leaves (host mark: no
+                    // weak leaf, no history flush before the block's last leaf), the list is full, and the f-chain that came down to this
+                    // leaf wrote the layers of size 4 and 2 into every lane's own slots. The leaf step above is complete: by the fast
+                    // path (nobody killed or cloned, every path took the bit its leaf favours) or (POLAR_R1_RANK) by a ranking step,
+                    // after which a clone holds its source's slot pointers and a path may carry the bit its leaf does not favour. If
+                    // the three leaves that follow take the fast path, every path just takes the bit its leaf favours, and the four steps are
+                    // one: the leaf values of positions 1..3 are computed here from those two layers, the fast-path test is run
+                    // for each of them in order on temporaries, and only if all three pass (in both lane groups) is anything committed.
+                    // Otherwise nothing was written — the guard distance of the f-node included, which is kept in a temporary — and the
+                    // loop goes on at phi + 1 as ever.
+                    //
+                    // The layers are read through the slot pointers, as the g-visit of the LDS layers reads them (polar_scl_visits.inc),
+                    // and the g-nodes get the bits the walk's partial sums would hold: u0 = the bit this path took at leaf 0 for
+                    // g(y0, y1); then (u0 ^ u1, u1) for the two g-nodes of the layer of 4 and u2 for the last leaf, where u1 and u2 are
+                    // the sign bits of the leaf values 1 and 2: a leaf on the fast path decides neg = signbit(v) && |v| != 1, and a block
+                    // in which a later leaf value of any active lane has |v| == 1.0 (LLR 0: it decides 0 whatever its sign) is left to
+                    // the loop. Same g_node_e, same operands, same bits as the walk: the values are the walk's. After a fast leaf 0 the
+                    // block is also given up over |leaf 0| == 1.0, as it was when those bits were taken from the operands' signs.
+                    PROF_CNT(29, 1)
+                    if (!fast) { PROF_CNT(36, 1) R1_CNT(2) }
+                    // (the control word of the leaf behind the quad, should it be finished here: asked for now, needed at the commit —
+                    // loaded at the top of the step it would be one more scalar held across the layer visits)
+                    const uint32_t ctl_r1 = ctlp[phi + 4 < N ? phi + 4 : 0];
+                    double lf[3] = {0.0, 0.0, 0.0};
+                    double gq = gacc;
+                    if (active) {
+                        const double *yq = lds_llr + (size_t)1 * 64 + gbase + pL.get(1), *xq = lds_llr + (size_t)3 * 64 + gbase + pL.get(2);      // layers of size 2, 4
+                        const double y0 = yq[0], y1 = yq[64], x0 = xq[0], x1 = xq[64], x2 = xq[128], x3 = xq[192];
+                        const unsigned s0 = ubit << 31;
+                        lf[0] = g_node_e(y0, y1, s0, tb);
+                        const unsigned s1 = (unsigned)__double2hiint(lf[0]);
+                        const double z0 = g_node_e(x0, x2, s0 ^ s1, tb), z1 = g_node_e(x1, x3, s1, tb);
+                        lf[1] = f_node_e_acc(z0, z1, gq);
+                        lf[2] = g_node_e(z0, z1, (unsigned)__double2hiint(lf[1]), tb);
+                    }
+                    // the fast-path tests in leaf order, on temporaries: metric of the good forks so far (pmq), the sufficient
+                    // test on the high words alone (see the step above). Where high words collide or the test fails the block is
+                    // left to the loop, which runs the exact reductions itself: giving up is always exact.
+                    double pmq = pm;
+                    auto tests = [&](const auto &lv, u64 m_one, uint32_t &uq) -> bool {
+                        constexpr int CNT = (int)(sizeof(lv) / sizeof(double));
+                        u64 m_lt = ~0ull;
+                        uq = 0;
+#pragma unroll
+                        for (int i_ = 0; i_ < CNT; ++i_) {
+                            bool ng1; double al1, sn1, sp1;
+                            leaf_terms<ED>(lv[i_], active, actw, tb, ng1, al1, sn1, sp1);
+                            const double gq_ = pmq + sn1, bq_ = (pmq + al1) * 0.99999999999909050530;
+                            unsigned gh_ = active ? (unsigned)__double2hiint(gq_) : 0u, bh_ = active ? (unsigned)__double2hiint(bq_) : 0xFFFFFFFFu;
+                            group_max_min_u32<GS>(gh_, bh_);
+                            m_lt &= __builtin_amdgcn_uicmp(gh_, bh_, 36);                          // ULT
+                            m_one |= __builtin_amdgcn_fcmp(fabs(lv[i_]), 1.0, 1);                  // OEQ
+                            pmq = gq_;
+                            uq |= (ng1 ? 1u : 0u) << i_;
+                        }
+                        const u64 m_okq = __builtin_amdgcn_sicmp(nact, 0, 32) | (__builtin_amdgcn_sicmp(nact, L, 32) & m_lt);
+                        return ((m_okq | ~group_result_rows<GS>()) == ~0ull) && (m_one & actw) == 0;
+                    };
+                    uint32_t uq;
+                    const bool pass = tests(lf, fast ? __builtin_amdgcn_fcmp(fabs(leaf), 1.0, 1) : 0ull, uq);
+                    if (pass) {
+                        PROF_CNT(30, 1)
+                        PROF_CNT(8, 3)
+                        PROF_CNT(9, 3)
+                        PROF_R1_COMMIT
+                        if (fast) { R1_CNT(0) } else { PROF_CNT(37, 1) R1_CNT(3) }
+                        const uint32_t u1 = uq & 1u, u2 = (uq >> 1) & 1u, u3 = uq >> 2;
+                        if (active) {
+                            pm = pmq;
+                            hword |= (u1 << ((t + 1) & 31)) | (u2 << ((t + 2) & 31)) | (u3 << ((t + 3) & 31));
+                        }
+                        gacc = gq;
+                        // the quad's partial sums, as the four calls of the leaf's own update would have left them: after leaf 1
+                        // the layer of size 2 holds (u0 ^ u1, u1), after leaf 3 the layer of size 4 gets that pair XOR (u2 ^ u3, u3)
+                        // followed by (u2 ^ u3, u3); from there exactly as the rate-0 block hands over its zeros
+                        uint32_t X = (ubit ^ u1 ^ u2 ^ u3) | ((u1 ^ u3) << 1) | ((u2 ^ u3) << 2) | (u3 << 3);
+                        int Sx = 4, adv = 3;
+                        uint32_t ctl_after = ctl_r1;
+                        bool octet_open = (ctl & 0x600u) == 0x600u;       // (instrumented build: the octet's leaf 4 is still a loop step)
+                        (void)octet_open;
+#if POLAR_R1_CHAIN
+                        if constexpr (LDS_LOG >= 3) {
+                        if ((ctl & 0x600u) == 0x600u && !prof_chain_off) {
+                            // ---- the second quad of a marked octet in the same step (rb == 3: no history flush before the octet's
+                            // last leaf). The quad just finished is the left half of the octet: X is column 0 of the layer of 4, and
+                            // the g-visit of that layer at leaf 4 would form its right half from the layer of 8 — read through its
+                            // slot pointer — with exactly these bits, the f-chain below it the layer of 2 and leaf 4. Here all of
+                            // that stays in registers; leaf 4 gets the same high-word test as the later leaves, leaves 5 .. 7 the
+                            // continuation above. If all four pass, eight leaves are committed at once and the octet's partial sums
+                            // go to the layer of 8 as a rate-0 block of 8 hands over its zeros: (X ^ X', X') for the two quads'
+                            // X, X'. (The layers of size 4 and 2 are not stored: nothing reads them before the next visit of the
+                            // layer of 4 rewrites them, as behind a rate-0 block of 8.) If anything fails nothing further is
+                            // written: the state after the first quad is a committed one, and the loop goes on at leaf 4.
+                            PROF_CNT(38, 1)
+                            R1_CNT(4)
+                            const uint32_t ctl_r2 = ctlp[phi + 8 < N ? phi + 8 : 0];
+                            double lc[4] = {0.0, 0.0, 0.0, 0.0};
+                            double gq2 = gq;
+                            if (active) {
+                                const double *wq = lds_llr + (size_t)7 * 64 + gbase + pL.get(3);      // layer of size 8
+                                double wa[4], wb[4], w[4];
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) { wa[j] = wq[(size_t)j * 64]; wb[j] = wq[(size_t)(j + 4) * 64]; }
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) w[j] = g_node_e(wa[j], wb[j], X << (31 - j), tb);
+                                const double y0 = f_node_e_acc(w[0], w[2], gq2), y1 = f_node_e_acc(w[1], w[3], gq2);
+                                lc[0] = f_node_e_acc(y0, y1, gq2);
+                                const unsigned s0 = (unsigned)__double2hiint(lc[0]);
+                                lc[1] = g_node_e(y0, y1, s0, tb);
+                                const unsigned s1 = (unsigned)__double2hiint(lc[1]);
+                                const double z0 = g_node_e(w[0], w[2], s0 ^ s1, tb), z1 = g_node_e(w[1], w[3], s1, tb);
+                                lc[2] = f_node_e_acc(z0, z1, gq2);
+                                lc[3] = g_node_e(z0, z1, (unsigned)__double2hiint(lc[2]), tb);
+                            }
+                            uint32_t uc;
+                            if (tests(lc, 0ull, uc)) {
+                                PROF_CNT(39, 1)
+                                PROF_CNT(8, 4)
+                                PROF_CNT(9, 4)
+                                R1_CNT(5)
+                                R1_CNT(0)
+                                const uint32_t u4 = uc & 1u, u5 = (uc >> 1) & 1u, u6 = (uc >> 2) & 1u, u7 = uc >> 3;
+                                if (active) {
+                                    pm = pmq;
+                                    hword |= (u4 << ((t + 4) & 31)) | (u5 << ((t + 5) & 31)) | (u6 << ((t + 6) & 31)) | (u7 << ((t + 7) & 31));
+                                }
+                                gacc = gq2;
+                                const uint32_t X2 = (u4 ^ u5 ^ u6 ^ u7) | ((u5 ^ u7) << 1) | ((u6 ^ u7) << 2) | (u7 << 3);
+                                X = (X ^ X2) | (X2 << 4);
+                                Sx = 8; adv = 7;
+                                ctl_after = ctl_r2;
+                                octet_open = false;
+                            }
+                        }
+                        }
+#endif
+                        PROF_R1_OCTET(octet_open)
+                        const int nu = phi >> (Sx == 8 ? 3 : 2);
+                        if ((nu & 1) == 0) {
+                            if (active) clsmall = (Sx == 8) ? ((clsmall & ~(0xFFull << 8)) | ((u64)X << 8)) : ((clsmall & ~(0xFull << 4)) | ((u64)X << 4));
+                        } else {
+                            update_c(Sx, X, nu);
+                        }
+                        wave_mem_fence();
+                        t += adv;
+                        phi += adv;
+                        ctl_next = ctl_after;
+                        r1_done = true;
+                    } else {
+                        if (fast) { R1_CNT(1) }
+                    }
+                    PROF(28)
+                }
+                }
+#endif
                 // every 32 unfrozen steps the decision word is stored together with the slot (`origin`) that
                 // holds this path's previous word: a linked list per path, walked once at the end, so that
                 // neither clones nor flushes ever copy history (the reference copies it on every clone,

@@ -6,7 +6,9 @@ before that leaf: the few-path head of DESIGN.md §4.
 The rate-1 block lines give the cycles of the loop iterations at positions 1 .. Z-1 of the host-marked all-unfrozen
 blocks of 4 and 8 leaves whose first leaf took the fast path: the most that finishing such a block in one step could remove.
 R1_OFF=1 keeps the list-of-32 kernels from finishing marked quads in one step (the marks stay: the lines above then describe the walk
-without the continuation); otherwise its own cycles and its tried / committed counts are printed."""
+without the continuation); otherwise its own cycles and its tried / committed counts are printed.
+R1_RANK_OFF=1 / R1_CHAIN_OFF=1 keep the continuation from starting after a ranked first leaf / from chaining the second quad of an octet:
+the two "sequel" lines then give the cycles of the loop iterations each of them would remove (profiles/r1chain)."""
 import ctypes as C
 import os
 import sys
@@ -34,14 +36,15 @@ torch.cuda.synchronize()
 prof.zero_()
 head_phi = int(os.environ.get("HEAD_PHI", "432"))
 prof[32] = head_phi                                       # (read by the kernel: PROF_HEAD_DECL)
-prof[33] = 1 if os.environ.get("R1_OFF") else 0          # (PROF_R1_DECL)
+prof[33] = (1 if os.environ.get("R1_OFF") else 0) | (2 if os.environ.get("R1_RANK_OFF") else 0) | (4 if os.environ.get("R1_CHAIN_OFF") else 0)      # (PROF_R1_DECL)
 torch.cuda.synchronize()
 import time
 t = time.perf_counter()
 g.decode_scl_llr_dev(llr.data_ptr(), B, L, out.data_ptr(), prof.data_ptr())
 torch.cuda.synchronize()
 dt = time.perf_counter() - t
-a = prof[:32].cpu().numpy().astype(float)
+a = prof[:42].cpu().numpy().astype(float)
+x = a[34:42]                                              # (the accumulators [32] .. [39] of the kernel: two words further up)
 names = ["loop ovh", "layer S>SL g (HBM)", "layer S>SL f (HBM)", "layer 4<=S<=SL (LDS)", "layer S<4", "leaf frozen / rate-0 block", "leaf unfrozen (rest: flush etc.)", "partial sums", "unf: DPP reductions+decision", "unf: competitive-bad loop", "unf: stack/srcof", "unf: clone shuffles+update", "-", "unf: setup+goods rank loop", "unf: wait for leaf (ballot)", "unf: softplus+bounds"]
 print(f"L={L} B={B} time {dt*1e3:.2f} ms -> {B/dt:.0f} cw/s")
 cyc = a[:8].sum() + a[16:22].sum() + a[28]                # ([22], [23]: the head split below, not phases; [28]: the quad continuation)
@@ -57,6 +60,14 @@ if a[25] + a[26] > 0 and a[23] > 0:
     print(f"  iterations 1..Z-1 of the blocks that started fast: {100*a[24]/a[23]:.2f}% of the leaf loop  {a[24]/nwd:10.0f} of {a[23]/nwd:.0f} cycles/wave-decode")
 if a[29] > 0:
     print(f"  quad continuation (per wave): tried {a[29]:.0f}, committed {100*a[30]/a[29]:.1f}%; {100*a[28]/cyc:.1f}% of the cycles  {a[28]/nwd:10.0f} cycles/wave-decode")
+if x[1] + x[3] > 0 and a[23] > 0:
+    print(f"  sequel (a) iterations 1..3 of marked quads whose leaf 0 was ranked, list full: {x[1]/nwd:.1f} quads/wave-decode  "
+          f"{100*x[0]/a[23]:.2f}% of the leaf loop  {x[0]/nwd:10.0f} cycles/wave-decode")
+    print(f"  sequel (b) leaf-4 iterations of marked octets whose first quad was committed: {x[3]/nwd:.1f} /wave-decode  "
+          f"{100*x[2]/a[23]:.2f}% of the leaf loop  {x[2]/nwd:10.0f} cycles/wave-decode")
+if x[4] + x[6] > 0:
+    print(f"  entry after a ranked leaf 0 (per wave-decode): tried {x[4]/nwd:.1f}, committed {x[5]/nwd:.1f}; "
+          f"chain: tried {x[6]/nwd:.1f}, committed {x[7]/nwd:.1f}")
 for nm, v in zip(names[:8], a[:8]):
     print(f"  {nm:34s} {100*v/cyc:5.1f}%  {v/nwd:10.0f} cycles/wave-decode")
 sub = ["unf: leaf wait + softplus + DPP bounds", "unf: fast path commit", "unf: goods rank loop", "unf: competitive-bad loop",
