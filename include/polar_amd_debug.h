@@ -58,6 +58,14 @@ long polar_debug_get(const polar_code_t *h, const char *key);
  * host-pointer call; no call yet). Below -1: -(1 + the hipError_t that stopped it). The buffers are the handle's: the answer is
  * valid until the next call on the handle. Both libraries. */
 long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap);
+/* The alive lists of the step-wise Monte-Carlo engine (polar_mc_batch, polar_mc_batch_ber, polar_mc_batch_bicm): the two buffers of
+ * trial indices that the points of a round hand to one another (the trials that failed at a point are the ones simulated at the next
+ * enabled point of the same list size). Copies min(count, cap) entries of buffer `which` (0 or 1), in no particular order, to `out`
+ * and returns the count; -1: the handle has no such buffers (no round yet), or `which` is neither; below -1: -(1 + hipError_t). After
+ * a round the two buffers hold what the last list size with an enabled point left: the failures of its last enabled point in one,
+ * what that point was given (the failures of the enabled point before it, or all T trials if it was the only one) in the other.
+ * Reads only; valid until the next call on the handle. Both libraries. */
+long polar_debug_mc_alive(polar_code_t *h, int which, uint64_t *out, long cap);
 /* The per-leaf control words as uploaded (marked != 0: with the rate-1 block field in bits 9-10, else the plain array the knob
  * "no_r1" selects): copies min(N, cap) words, returns N; below 0: -(1 + hipError_t). Both libraries. polar_debug_get
  * "r1_committed" / "r1_discarded" (test build only): the rate-1 quad continuations the last list-of-32 launch of the handle's

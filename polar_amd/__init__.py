@@ -254,6 +254,25 @@ class PolarCode:
             raise PolarError("polar_debug_fallback_rows: the count changed between two reads")
         return np.sort(rows[:n])
 
+    def debug_mc_alive(self):
+        """The two alive lists as the handle's last mc_batch / mc_batch_ber / mc_batch_bicm round left them (polar_debug_mc_alive):
+        a pair of sorted uint64 arrays of trial indices, in buffer order; None before the first round."""
+        f = self._L.polar_debug_mc_alive
+        f.restype = C.c_long
+        f.argtypes = [C.c_void_p, C.c_int, _u64p, C.c_long]
+        lists = []
+        for which in (0, 1):
+            n = int(f(self._h, which, None, 0))
+            if n == -1:
+                return None
+            if n < 0:
+                raise PolarError(f"polar_debug_mc_alive: HIP status {-n - 1}")
+            a = np.zeros(max(n, 1), np.uint64)
+            if int(f(self._h, which, _p(a, _u64p), n)) != n:
+                raise PolarError("polar_debug_mc_alive: the count changed between two reads")
+            lists.append(np.sort(a[:n]))
+        return tuple(lists)
+
     def debug_ctl_words(self, marked=True):
         """The per-leaf control words as uploaded (polar_debug_ctl_words): the array with the rate-1 block field, or the plain one."""
         f = self._L.polar_debug_ctl_words

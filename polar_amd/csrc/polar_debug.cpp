@@ -155,6 +155,21 @@ long polar_debug_fallback_rows(polar_code_t *h, uint32_t *rows, long cap) {
     return e == hipSuccess ? (long)count : -(long)e - 1;
 }
 
+// One of the two alive lists of the step-wise Monte-Carlo engine (polar_mc_batch*: mc_round_launch, polar_montecarlo.cpp) as the
+// handle's last round left it: copies min(count, cap) trial indices (in no particular order) to `out` and returns the count.
+// Reads only; the engine's calls have synchronised their stream before they return.
+long polar_debug_mc_alive(polar_code_t *h, int which, uint64_t *out, long cap) {
+    if (!h || which < 0 || which > 1 || !h->d_alive[which].p || !h->d_nalive.p) return -1;
+    DevGuard dg_;
+    if (ensure_device(h, dg_)) return -1;
+    unsigned int count = 0;
+    hipError_t e = hipMemcpy(&count, h->d_nalive.p + which, sizeof count, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (size_t)count > h->d_alive[which].cap) return -(long)hipErrorInvalidValue - 1;      // (a count no round can leave)
+    const long n = std::min<long>(count, cap);
+    if (e == hipSuccess && out && n > 0) e = hipMemcpy(out, h->d_alive[which].p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? (long)count : -(long)e - 1;
+}
+
 // The control words as they were uploaded (marked != 0: the array with the rate-1 block field, else the plain one): copies
 // min(N, cap) words to `words`, returns N; below 0: -(1 + hipError_t). Both libraries.
 long polar_debug_ctl_words(polar_code_t *h, uint32_t *words, long cap, int marked) {

@@ -202,6 +202,19 @@ class Oracle(_Base):
                    C.c_double(snr_db), _p(llr, _dp), _p(info, _u8p))
         return llr, info
 
+    def synth_llr_trials(self, seed, trials, s, cid=0):
+        """(llr, info) of the given trial indices (uint64, any order), one orc_synth_llr call per trial; cid != 0: the ASK / BICM
+        front end (orc_synth_bicm_llr) with `s` read as the SNR in dB."""
+        trials = np.asarray(trials, np.uint64)
+        llr = np.zeros((len(trials), self.N), np.float64)
+        info = np.zeros((len(trials), self.K), np.uint8)
+        for r, t in enumerate(trials):
+            if cid == 0:
+                self._call("synth_llr", C.c_uint64(seed), C.c_uint64(int(t)), C.c_double(s), _p(llr[r], _dp), _p(info[r], _u8p))
+            else:
+                self._call("synth_bicm_llr", C.c_int(cid), C.c_uint64(seed), C.c_uint64(int(t)), C.c_double(s), _p(llr[r], _dp), _p(info[r], _u8p))
+        return llr, info
+
     def mc_batch(self, seed, t0, T, stride, ebno, Ls, enabled, err, run):
         ebno = np.ascontiguousarray(ebno, np.float64)
         Ls = np.ascontiguousarray(Ls, np.uint8)

@@ -31,7 +31,7 @@ def test_exports_every_declared_symbol(built_lib):
     from polar_amd import build
     api, dbg = _declared("polar_amd.h"), _declared("polar_amd_debug.h")
     assert len(api) >= 25 and "polar_debug_set" in dbg and not [n for n in api if n.startswith("polar_debug")]
-    assert "polar_debug_fallback_rows" in dbg
+    assert "polar_debug_fallback_rows" in dbg and "polar_debug_mc_alive" in dbg
     assert "polar_amd_debug.h" not in re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "polar_amd.h")).read(), flags=re.S)
     for path in (built_lib, build.build_test()):
         lib = C.CDLL(path)
@@ -63,6 +63,7 @@ def test_fault_injection_exists_only_in_the_test_build(built_lib):
     assert g.debug_get("lat_waves") == 0                                # (a key of both libraries: no decode call yet)
     assert g.debug_get("lane_waves") == 0
     assert g.debug_fallback_rows() is None                              # (polar_debug_fallback_rows: -1 before any decode call)
+    assert g.debug_mc_alive() is None                                   # (polar_debug_mc_alive: -1 before any Monte-Carlo round)
     try:
         polar_amd.use_library(build.build_test())
         t = polar_amd.PolarCode(5, 16, 0.32, 0)
