@@ -299,6 +299,50 @@ int polar_decode_sc_flip_batch(polar_code_t *h, const void *llr, int fmt, long B
 int polar_mc_batch_flip(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis,
                         int n_e, int max_flips, const uint8_t *enabled /*[n_e]*/, uint64_t *stats /*[n_e][POLAR_FL_N], ADDED to*/);
 
+/* ---- SCAN: soft-output decoding by soft cancellation (Fayyaz, Barry 2014) ----
+ * (no member of the reference's class.) The SC schedule with LLRs passed in both directions, `iters` (1 .. POLAR_SCAN_MAX_ITERS) times.
+ * Layer 0 is the channel row, layer n the N leaves in decoding order — the index space of polar_get_frozen / polar_get_order; node v of
+ * layer lam has N >> lam values and the children 2v (left) and 2v + 1 (right), which pair its neighbouring elements 2j, 2j + 1. Every
+ * node carries L (towards the leaves; at layer 0 the caller's row) and B (towards the channel). A leaf's B is +inf if frozen, else 0;
+ * every internal B is 0 before iteration 1. One iteration is one depth-first walk; at a node with values a, a0 = a[2j], a1 = a[2j+1]:
+ *   L_left[j]  = f(a0, a1 + B_right[j])       (B_right: the previous iteration's)      ... the left child, which yields B_left ...
+ *   L_right[j] = f(a0, B_left[j]) + a1                                                 ... the right child, which yields B_right ...
+ *   B[2j]      = f(B_left[j], B_right[j] + a1),   B[2j+1] = f(B_left[j], a0) + B_right[j]
+ * f is the f-node of decode_scl_llr (the reference's boxplus below 40, min-sum from 40 on; PolarCode.cpp:437-446) or, with
+ * POLAR_SCAN_MINSUM, f(a, b) = sgn(a) sgn(b) min(|a|, |b|) with +0 where the min is 0. After the last iteration that ran:
+ *   info_llr[B][K] double  info_llr[i] = the leaf L at order[i]
+ *   out[B][K] uint8        out[i] = (info_llr[i] < 0): a zero of either sign decides 0
+ *   ext[B][N] double       the B of layer 0: the extrinsic LLRs of the coded bits, indexed like the row (+inf where the frozen set alone
+ *                          fixes a coded bit); the a-posteriori value is llr + ext
+ *   crc_ok[B] uint8        the decided check bits at order[K .. K + crc) equal those the CRC matrix gives for out; 1 where crc == 0
+ *   n_iter[B] uint8        the iterations that ran: `iters`, or with POLAR_SCAN_EARLY_STOP (crc > 0 only) the first whose decisions pass
+ *                          the CRC — that iteration is the last
+ * Rows must be finite. out / d_out is required, the other four may be NULL. One kernel, one codeword per wave with its whole state in
+ * LDS: n <= 11 (POLAR_E_UNSUPPORTED above, before the device is touched). polar_set_mode and polar_set_tuning do not affect it.
+ * POLAR_E_ARG, before the device is touched: NULL handle / rows / out, iters out of range, unknown flag bits, POLAR_SCAN_EARLY_STOP on a
+ * handle with crc == 0, unknown fmt, 16-bit rows at an odd address, negative B; B = 0 is POLAR_OK.
+ *   _dev   device pointers, stream-ordered on `stream`, no host synchronisation: ONE launch. Two calls on one handle and one stream
+ *          need nothing between them. The first call of a handle uploads the kernel's schedule.
+ *   host   host pointers: one copy of all B rows in, the launch, a wait, the copies out.
+ * polar_mc_batch_scan: like polar_mc_batch_flip: every ENABLED point of `axis` simulates all the trials {t0 + i*stride : i < T} and ADDS
+ * to stats[ie*POLAR_SN_N + c] (host uint64). `constellation` as polar_mc_batch_list; POLAR_RX_MLC, NULL pointers, iters or flags out of
+ * range, negative T, stride < 1: POLAR_E_ARG before the device is touched; T = 0 is POLAR_OK and leaves stats alone. */
+#define POLAR_SCAN_MINSUM 1
+#define POLAR_SCAN_EARLY_STOP 2
+#define POLAR_SCAN_MAX_ITERS 32
+int polar_decode_scan_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, int iters, int flags, uint8_t *d_out /*[B][K]*/,
+                                double *d_info_llr /*[B][K]*/, double *d_ext /*[B][N]*/, uint8_t *d_crc_ok /*[B]*/,
+                                uint8_t *d_n_iter /*[B]*/, void *stream);
+int polar_decode_scan_batch(polar_code_t *h, const void *llr, int fmt, long B, int iters, int flags, uint8_t *out, double *info_llr,
+                            double *ext, uint8_t *crc_ok, uint8_t *n_iter);
+#define POLAR_SN_RUN 0      /* every trial */
+#define POLAR_SN_ERR 1      /* decided word differs from the sent info */
+#define POLAR_SN_UNDET 2    /* ERR on a code with a CRC, and crc_ok = 1 */
+#define POLAR_SN_ITERS 3    /* sum of n_iter */
+#define POLAR_SN_N 4
+int polar_mc_batch_scan(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis,
+                        int n_e, int iters, int flags, const uint8_t *enabled /*[n_e]*/, uint64_t *stats /*[n_e][POLAR_SN_N], ADDED to*/);
+
 /* ---- PolarCode::decode_scl_p1(PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);

@@ -45,7 +45,7 @@ int polar_debug_set(polar_code_t *h, const char *key, long value);
  * "mode_override", "head_phi" (hand-over leaf of the handle's last decode_scl_llr launch, 0 = decoded in one phase),
  * "lat_waves" (blocks of the one-codeword-per-wave launch of the handle's last decode_scl_llr / decode_sc_p1 / decode_mlc call, 0 = it
  * took no such kernel, or was a pipelined host-pointer call, whose chunks are decoded on contexts of their own), "lane_waves" (blocks of
- * the codeword-per-lane launch of the handle's last decode_scl_p1 / decode_sc_p1 / decode_mlc call, 0 = it launched none), "last_rounds", "last_round_max_per_device", "worker_threads_started", "multi_poisoned",
+ * the codeword-per-lane launch of the handle's last decode_scl_p1 / decode_sc_p1 / decode_mlc call, 0 = it launched none), "scan_grid_cap" (most blocks of a polar_decode_scan_batch launch; its waves loop over the rest of the rows), "last_rounds", "last_round_max_per_device", "worker_threads_started", "multi_poisoned",
  * "round_us_first|min|median|max|count" (steps of the handle's last sweep), "host_chunks", "host_chunk_cw", "host_lanes",
  * "host_threads", "host_us_copy_in|wait|copy_out|total" (the last pipelined host-pointer call), "test_hooks" (1 in the test
  * build); -1 = unknown key. Test build only: "head_check" reads the hand-over records of the handle's last two-phase decode back

@@ -41,6 +41,8 @@ AD_RUN, AD_ERR, AD_UNDET, AD_STAGE0 = 0, 1, 2, 3     # include/polar_amd.h POLAR
 AD_MAX_STAGES = 8
 FL_RUN, FL_ERR, FL_UNDET, FL_FIRST, FL_FLIPPED, FL_DECODES, FL_N = 0, 1, 2, 3, 4, 5, 6     # include/polar_amd.h POLAR_FL_*: columns of the SC-Flip statistics
 FLIP_MAX = 64
+SN_RUN, SN_ERR, SN_UNDET, SN_ITERS, SN_N = 0, 1, 2, 3, 4     # include/polar_amd.h POLAR_SN_*: columns of the SCAN statistics
+SCAN_MINSUM, SCAN_EARLY_STOP, SCAN_MAX_ITERS = 1, 2, 32      # include/polar_amd.h POLAR_SCAN_*
 
 
 def _llr_fmt_code(fmt):
@@ -71,6 +73,10 @@ def _llr_rows(llr, fmt):
     else:
         code, a = LLR_F64, np.ascontiguousarray(llr, np.float64)
     return code, a
+
+
+def _scan_flags(minsum, early_stop):
+    return (SCAN_MINSUM if minsum else 0) | (SCAN_EARLY_STOP if early_stop else 0)
 
 
 def _rx_flag(receiver):
@@ -741,6 +747,66 @@ class PolarCode:
         res = {"stats": stats}
         for name, col in (("bler", FL_ERR), ("undetected_rate", FL_UNDET), ("first_share", FL_FIRST), ("flipped_share", FL_FLIPPED),
                           ("mean_decodes", FL_DECODES)):
+            res[name] = stats[:, col] / run
+        return res
+
+    def decode_scan(self, llr, iters=4, fmt=None, minsum=False, early_stop=False):
+        """SCAN soft-output decoding (polar_decode_scan_batch): the SC schedule with LLRs passed in both directions, `iters` (1 .. 32)
+        times. Returns (out [B, K] uint8, info_llr [B, K] float64, ext [B, N] float64, crc_ok [B] uint8, n_iter [B] uint8): the hard
+        word, the LLRs of the info bits (out = info_llr < 0), the extrinsic LLRs of the coded bits, indexed like the row (+inf where
+        the frozen set alone fixes a bit; a posteriori: llr + ext), whether the decided check bits are the CRC's (1 without a CRC),
+        and the iterations that ran. minsum: f(a, b) = sgn sgn min instead of the f-node of decode_scl_llr; early_stop (needs a CRC):
+        the first iteration whose decisions pass the CRC is the last. `llr` and `fmt` as decode_scl_llr_list; a single row [N] is a
+        batch of one. Rows must be finite; n <= 11."""
+        code, a = _llr_rows(llr, fmt)
+        a2 = a.reshape(-1, self.N)
+        B = a2.shape[0]
+        out = np.zeros((B, self.K), np.uint8)
+        info_llr = np.zeros((B, self.K), np.float64)
+        ext = np.zeros((B, self.N), np.float64)
+        crc_ok = np.zeros(B, np.uint8)
+        n_iter = np.zeros(B, np.uint8)
+        self._chk(self._L.polar_decode_scan_batch(
+            self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), C.c_int(iters), C.c_int(_scan_flags(minsum, early_stop)),
+            _p(out, _u8p), C.c_void_p(info_llr.ctypes.data), C.c_void_p(ext.ctypes.data), C.c_void_p(crc_ok.ctypes.data),
+            C.c_void_p(n_iter.ctypes.data)))
+        return out, info_llr, ext, crc_ok, n_iter
+
+    def decode_scan_dev(self, llr_ptr, fmt, B, iters, out_ptr, info_llr_ptr=0, ext_ptr=0, crc_ok_ptr=0, n_iter_ptr=0, minsum=False,
+                        early_stop=False, stream=None):
+        """Device-resident form (polar_decode_scan_batch_dev): LLRs [B, N] of format `fmt` -> out uint8 [B, K] and, where a pointer is
+        given, info_llr float64 [B, K], ext float64 [B, N], crc_ok uint8 [B], n_iter uint8 [B]; asynchronous on `stream`, one launch."""
+        self._chk(self._L.polar_decode_scan_batch_dev(
+            self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B), C.c_int(iters), C.c_int(_scan_flags(minsum, early_stop)),
+            C.c_void_p(out_ptr), C.c_void_p(info_llr_ptr), C.c_void_p(ext_ptr), C.c_void_p(crc_ok_ptr), C.c_void_p(n_iter_ptr),
+            _stream_ptr(stream)))
+
+    def mc_batch_scan(self, seed, t0, T, stride, axis, iters, enabled, stats, minsum=False, early_stop=False, constellation=0):
+        """polar_mc_batch_scan: the trials {t0 + i*stride : i < T} of every enabled point ADD to stats, uint64 [len(axis), 4] = SN_RUN,
+        SN_ERR, SN_UNDET, SN_ITERS. constellation 0: BPSK, `axis` = Eb/N0 in dB; an ASK constellation: the BICM front end, `axis` =
+        SNR in dB."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        enabled = np.ascontiguousarray(enabled, np.uint8)
+        if stats.dtype != np.uint64 or stats.size != len(ax) * SN_N or not stats.flags.c_contiguous:
+            raise PolarError("stats must be a C-contiguous uint64 array [len(axis), %d]" % SN_N)
+        if enabled.size != len(ax):
+            raise PolarError("enabled must have len(axis) entries")
+        self._chk(self._L.polar_mc_batch_scan(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(t0),
+                                              C.c_long(T), C.c_long(stride), _p(ax, _dp), C.c_int(len(ax)), C.c_int(iters),
+                                              C.c_int(_scan_flags(minsum, early_stop)), _p(enabled, _u8p), _p(stats, _u64p)))
+
+    def scan_stats(self, axis, iters=4, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0, minsum=False, early_stop=False):
+        """The SCAN decoder over a sweep: rounds of mc_batch_scan, sized and stopped like list_stats' (_stat_rounds). Returns a dict:
+        `stats` uint64 [len(axis), 4] (SN_* columns), `bler`, `undetected_rate` = ERR, UNDET over RUN, and `mean_iters` = ITERS over
+        RUN: the iterations a codeword took on average, all float64 [len(axis)]."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        stats = np.zeros((len(ax), SN_N), np.uint64)
+        self._stat_rounds("scan_stats", lambda t0, T, enabled: self.mc_batch_scan(seed, t0, T, 1, ax, iters, enabled, stats, minsum,
+                                                                                   early_stop, constellation),
+                          stats, SN_ERR, SN_RUN, max_runs, max_err, batch)
+        run = np.maximum(stats[:, SN_RUN], 1).astype(np.float64)
+        res = {"stats": stats}
+        for name, col in (("bler", SN_ERR), ("undetected_rate", SN_UNDET), ("mean_iters", SN_ITERS)):
             res[name] = stats[:, col] / run
         return res
 

@@ -251,6 +251,54 @@ public:
         }
         return r;
     }
+    // SCAN soft-output decoding (polar_decode_scan_batch; B codewords back to back): the SC schedule with LLRs passed in both directions,
+    // `iters` (1 .. POLAR_SCAN_MAX_ITERS) times; flags: POLAR_SCAN_MINSUM | POLAR_SCAN_EARLY_STOP (the latter needs a CRC). info_llr:
+    // the LLRs of the info bits (out = info_llr < 0); ext: the extrinsic LLRs of the coded bits, indexed like the row (a posteriori:
+    // llr + ext); n_iter: the iterations that ran. Rows must be finite; block_length <= 2048.
+    struct ScanResult {
+        long B = 0;
+        int K = 0, N = 0;
+        std::vector<uint8_t> out;        // [B][K]
+        std::vector<double> info_llr;    // [B][K]
+        std::vector<double> ext;         // [B][N]
+        std::vector<uint8_t> crc_ok;     // [B]
+        std::vector<uint8_t> n_iter;     // [B]
+    };
+    ScanResult decode_scan(const std::vector<double> &llr, int iters = 4, int flags = 0) {
+        need(llr.size() % _block_length == 0, "decode_scan: size must be a multiple of block_length");
+        need(iters >= 1 && iters <= POLAR_SCAN_MAX_ITERS, "decode_scan: iters out of range");
+        ScanResult r;
+        r.B = (long)(llr.size() / _block_length); r.K = _info_length; r.N = _block_length;
+        r.out.resize((size_t)r.B * r.K); r.info_llr.resize((size_t)r.B * r.K); r.ext.resize((size_t)r.B * r.N);
+        r.crc_ok.resize((size_t)r.B); r.n_iter.resize((size_t)r.B);
+        check(polar_decode_scan_batch(_h, llr.data(), POLAR_LLR_F64, r.B, iters, flags, r.out.data(), r.info_llr.data(), r.ext.data(),
+                                      r.crc_ok.data(), r.n_iter.data()));
+        return r;
+    }
+    // The SCAN decoder over a sweep (polar_mc_batch_scan in rounds, stopped like list_stats). stats is [point * POLAR_SN_N +
+    // POLAR_SN_*]; mean_iters[point] = ITERS / RUN: the iterations a codeword took on average.
+    struct ScanStats {
+        int n_points = 0;
+        std::vector<uint64_t> stats;
+        std::vector<double> bler, undetected_rate, mean_iters;
+    };
+    ScanStats scan_stats(const std::vector<double> &axis, int iters = 4, int flags = 0, long max_runs = 1000, long max_err = 100,
+                         uint64_t seed = 0, long batch = 0, int constellation = 0) {
+        ScanStats r;
+        r.n_points = (int)axis.size();
+        const size_t P = axis.size(), C = POLAR_SN_N;
+        r.stats.assign(P * C, 0);
+        stat_rounds("scan_stats", r.stats, C, POLAR_SN_ERR, POLAR_SN_RUN, max_runs, max_err, batch, [&](long t0, long T, const uint8_t *enabled) {
+            return polar_mc_batch_scan(_h, constellation, seed, (uint64_t)t0, T, 1, axis.data(), r.n_points, iters, flags, enabled, r.stats.data());
+        });
+        r.bler.resize(P); r.undetected_rate.resize(P); r.mean_iters.resize(P);
+        for (size_t i = 0; i < P; ++i) {
+            const uint64_t *s = &r.stats[i * C];
+            const double run = s[POLAR_SN_RUN] ? (double)s[POLAR_SN_RUN] : 1.0;
+            r.bler[i] = s[POLAR_SN_ERR] / run; r.undetected_rate[i] = s[POLAR_SN_UNDET] / run; r.mean_iters[i] = s[POLAR_SN_ITERS] / run;
+        }
+        return r;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

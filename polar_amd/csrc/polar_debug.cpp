@@ -77,6 +77,7 @@ long polar_debug_get(const polar_code_t *h, const char *key) {
     if (s == "head_phi") return h->last_head_phi;
     if (s == "lat_waves") return h->last_lat_waves;
     if (s == "lane_waves") return h->last_lane_waves;
+    if (s == "scan_grid_cap") return polar_scan_grid_cap();
 #ifdef POLAR_TEST_HOOKS
     if (s == "head_check") {
         // The premise of the two-phase decode, checked on what the head really left: row 2 of every record of the handle's last

@@ -10,6 +10,7 @@
 //                         the list statistics of the sweep (polar_mc_batch_list)
 //   polar_adaptive.cpp    adaptive list decoding: a schedule of list sizes, escalated until the CRC passes, and its sweep
 //   polar_flip.cpp        SC-Flip: CRC-aided single-bit retries of SC decoding, and its sweep
+//   polar_scan.cpp        SCAN: soft-output decoding by soft cancellation, and its sweep
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction;
 //                         the walk the sweeps of polar_list.cpp and polar_adaptive.cpp share (sweep_begin, sweep_walk)
@@ -280,6 +281,8 @@ struct polar_code {
     std::vector<uint32_t> flip_ops;  // SC-Flip: the walk of sc_flip_kernel (PolarFlipParams::ops), built and uploaded by the first call (polar_flip.cpp)
     DevBuf<uint32_t> d_flip_ops;
     DevBuf<int32_t> d_flip_i32;      //   host form and sweep: flip [B] and cand [B][T]
+    std::vector<uint32_t> scan_ops;  // SCAN: the walk of scan_kernel (PolarScanParams::ops), built and uploaded by the first call (polar_scan.cpp)
+    DevBuf<uint32_t> d_scan_ops;
     DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never
@@ -468,7 +471,7 @@ void fill_demap(int cid, int N, double n0, PolarDemapParams &p);
 int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, long B, hipStream_t st, const double **d_llr);
 // polar_montecarlo.cpp — the channel of a sweep point in synth_kernel's parameters: BPSK at an Eb/N0 (constellation 0) or ASK / BICM at an SNR, both in dB
 void fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point);
-// The walk polar_mc_batch_list, polar_mc_batch_adaptive and polar_mc_batch_flip share. A cell: one enabled entry — its point of the axis, its chunk
+// The walk polar_mc_batch_list, polar_mc_batch_adaptive, polar_mc_batch_flip and polar_mc_batch_scan share. A cell: one enabled entry — its point of the axis, its chunk
 // length, its `width` counters at `ctr` in d_mc_ctr and in `stats`
 struct Sweep { polar_code *h; int cid; uint64_t seed, t0; long T, stride; const double *axis; uint64_t *stats; DevGuard dg; };
 struct SweepCell { int point; long chunk; size_t ctr; int width; };

@@ -253,6 +253,43 @@ hipError_t polar_launch_sc_flip(const PolarFlipParams &p, int grid, hipStream_t 
 // ctr[0 .. POLAR_FL_N) are ADDED to
 hipError_t polar_launch_flip_classify(const uint8_t *out, const uint8_t *crc_ok, const uint8_t *n_dec, const uint8_t *sent, long B, int K,
                                       unsigned long long *ctr, hipStream_t st);
+// SCAN soft-output decoding (polar_kernels_scan.hip; include/polar_amd.h polar_decode_scan_batch_dev): one codeword per
+// wave, the whole state in LDS (polar_scan_lds_bytes(n) must fit: n <= polar_scan_max_log()). ops: the walk over the code tree, a word
+// = type | lam << 3 | v << 7 | kl << 23 | kr << 25 | wb << 27: LEFT / RIGHT produce the L of a child of layer lam of the parent v; UP
+// the B of node v of layer lam; PAIR the leaf LLRs of node v of layer n - 1 and, with wb, its B. kl, kr: what the left and the right
+// child (PAIR: leaf) are — MIXED (its B is stored), all FROZEN (B = +inf), all UNFROZEN (B = 0).
+#define POLAR_SCAN_OP_LEFT 0
+#define POLAR_SCAN_OP_RIGHT 1
+#define POLAR_SCAN_OP_UP 2
+#define POLAR_SCAN_OP_PAIR 3
+#define POLAR_SCAN_KIND_MIXED 0
+#define POLAR_SCAN_KIND_FROZEN 1
+#define POLAR_SCAN_KIND_UNFROZEN 2
+#define POLAR_SCAN_F_MINSUM 1    // (the values of include/polar_amd.h POLAR_SCAN_MINSUM, POLAR_SCAN_EARLY_STOP)
+#define POLAR_SCAN_F_EARLY 2
+struct PolarScanParams {
+    int n, N, K, crc, iters, flags;
+    long B;
+    const void *llr;             // [B][N] device, elements of llr_fmt (POLAR_LLR_*)
+    int llr_fmt;
+    const uint32_t *ops;         // [n_ops] device
+    int n_ops;
+    const uint16_t *order;       // [N] device
+    const uint8_t *crcm;         // [crc][K] device
+    const double *tabs;          // [322] device (exact arithmetic only)
+    uint8_t *out;                // [B][K] device
+    double *info_llr;            // [B][K] device or nullptr
+    double *ext;                 // [B][N] device or nullptr
+    uint8_t *crc_ok, *n_iter;    // [B] device or nullptr
+};
+size_t polar_scan_lds_bytes(int n);
+int polar_scan_max_log();
+int polar_scan_grid_cap();       // most blocks of a launch; the waves loop over the rest of the rows
+hipError_t polar_launch_scan(const PolarScanParams &p, int grid, hipStream_t st);
+// The counters of the SCAN sweep (include/polar_amd.h POLAR_SN_*): decided words out [B][K] against the sent info [B][K];
+// ctr[0 .. POLAR_SN_N) are ADDED to
+hipError_t polar_launch_scan_classify(const uint8_t *out, const uint8_t *crc_ok, const uint8_t *n_iter, const uint8_t *sent, long B, int K,
+                                      int has_crc, unsigned long long *ctr, hipStream_t st);
 // Monte-Carlo round on the device (PolarCode.cpp:728-742, 758-769): alive[i] = t0 + i*stride, *n = T
 hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T, hipStream_t st);
 // rows [0, min(B, *n_in)): block error iff decoded != sent; ctr[0] += block errors, ctr[1] += differing bits
