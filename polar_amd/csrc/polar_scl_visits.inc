@@ -10,6 +10,11 @@
                 // lanes of each path. Round 6: a lone wave pays 4 cycles for EVERY instruction it issues, scalar or vector, 20 for a
                 // taken branch and ~ 50-60 for an LDS round trip (tools/lone_wave_microbench.hip), so the two lowest layers — three
                 // quarters of all visits — are straight-line code on registers outside the layer loop.
+                // (ED) The lanes of a path that is NOT active run the visits below all the same, on whatever their slot pointers lead to —
+                // at a layer this codeword has not written in that slot yet, the values the wave's PREVIOUS codeword left there. Nothing
+                // they compute is stored, but their guard distance would be kept: a codeword that follows one with an f-node in the
+                // window would be flagged with it. Only what a living path evaluates counts.
+                [[maybe_unused]] const double gacc_in = gacc;
                 const bool bottom_regs = n >= 3;
                 const int lam_hi = bottom_regs ? (lam_stop < n - 2 ? lam_stop : n - 2) : lam_stop;
                 for (int lam = lam_top; lam <= lam_hi; ++lam) {
@@ -80,6 +85,7 @@
                     }
                     PROF(4)
                 }
+                if constexpr (ED) { if (!active) gacc = gacc_in; }
             } else
             for (int lam = lam_top; lam <= lam_stop; ++lam) {
                 if (POLAR_UNLIKELY2(tbl && lam <= 2 && phi >= S2)) {

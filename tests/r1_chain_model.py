@@ -30,8 +30,10 @@ def full_before(frozen, L):
     return (2.0 ** np.minimum(t, 62)) >= L
 
 
-def walk(frozen, tests, L, rb, start=0, rank=True, chain=True):
-    """One launch whose per-codeword leaf tests (r1_model.leaf_tests) are `tests`, walked from leaf `start` -> dict of KEYS."""
+def walk(frozen, tests, L, rb, start=0, rank=True, chain=True, finished=None):
+    """One launch whose per-codeword leaf tests (r1_model.leaf_tests) are `tests`, walked from leaf `start` -> dict of KEYS.
+    finished: a list that receives (the wave's first row, first leaf, "quad" | "chain") per block finished in one step — "chain": the
+    second quad of the octet at that leaf, finished in the step of the first."""
     frozen = np.asarray(frozen, np.uint8)
     N = len(frozen)
     full = full_before(frozen, L)
@@ -66,25 +68,29 @@ def walk(frozen, tests, L, rb, start=0, rank=True, chain=True):
             if not done:
                 phi += 1
                 continue
+            if finished is not None:
+                finished.append((w, phi, "quad"))
             if chain and rb[phi] == 3:
                 c["bodies"] += 1
                 c["chain_tried"] += 1
                 if later(phi + 4, phi + 8):
                     c["chain_committed"] += 1
                     c["committed"] += 1
+                    if finished is not None:
+                        finished.append((w, phi, "chain"))
                     c["rank_then_chain"] += 1 if ranked else 0
                     phi += 4
             phi += 4
     return c
 
 
-def counts(frozen, llr_rows, L, rb=None, start=0, rank=True, chain=True, tests=None):
+def counts(frozen, llr_rows, L, rb=None, start=0, rank=True, chain=True, tests=None, finished=None):
     """dict of KEYS for one launch over the rows [B, N]. `tests`: the rows' leaf tests when the caller has them already."""
     frozen = np.asarray(frozen, np.uint8)
     rb = r1_model.marks(frozen, r1_model.weak_leaves(frozen)) if rb is None else rb
     if tests is None:
         tests = [r1_model.leaf_tests(frozen, r, L) for r in np.asarray(llr_rows, np.float64)]
-    return walk(frozen, tests, L, rb, start, rank, chain)
+    return walk(frozen, tests, L, rb, start, rank, chain, finished)
 
 
 def six(c):

@@ -36,9 +36,7 @@ class _Case:
         C.CDLL(None).srand(C.c_uint(1))
         self.g = polar_amd.PolarCode(n, K, G.EPS, crc)
         assert self.g.weak_leaves == 0
-        b = G.B_LARGE if key == LARGE else G.B
-        self.base = self.o.synth_llr(G.CODES[key], 0, b, self.o.snr_sqrt_linear(G.EBNO))[0]
-        self.base.setflags(write=False)
+        self.base = G.base_rows(self.o, key)
         self._want = {}
 
     def want(self, rows, fmt, L, b, tag):
