@@ -27,6 +27,22 @@ def test_oracle_equals_reference(oracle_built, n, K, crc):
             assert (r.decode_scl_llr(llr, L) == o.decode_scl_llr(llr, L)).all()
 
 
+@pytest.mark.parametrize("code", [(8, 128, 8), (9, 128, 8), (10, 512, 8), (10, 256, 8)])
+def test_oracle_equals_reference_on_tie_rows(oracle_built, code):
+    """Rows of one magnitude (tests/tie_numpy.py): almost every fork sits on a tie, the index rule decides. And the +-1 / +-3 rows
+    of tests/test_gpu_r1_block.py, which rounding noise decides, at the list sizes the oracle was compared at by hand."""
+    import tie_numpy
+    o, _, x = tie_numpy.case(code)
+    libc.srand(1)
+    r = oracle_lib.Reference(*code[:2], 0.32, code[2])
+    for L in tie_numpy.TIE_CODES[code][1]:
+        assert (r.decode_scl_llr(x, L) == o.decode_scl_llr(x, L)).all()
+    if code == (8, 128, 8):
+        x = tie_numpy.pm1_pm3_rows(o)
+        for L in (1, 2, 4, 8, 32):
+            assert (r.decode_scl_llr(x, L) == o.decode_scl_llr(x, L)).all()
+
+
 def test_probability_domain_equals_reference(oracle_built):
     libc.srand(1)
     r = oracle_lib.Reference(8, 128, 0.32, 4)
