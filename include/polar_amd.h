@@ -343,6 +343,63 @@ int polar_decode_scan_batch(polar_code_t *h, const void *llr, int fmt, long B, i
 int polar_mc_batch_scan(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis,
                         int n_e, int iters, int flags, const uint8_t *enabled /*[n_e]*/, uint64_t *stats /*[n_e][POLAR_SN_N], ADDED to*/);
 
+/* ---- systematic polar coding (Arikan 2011) ----
+ * (no member of the reference's class.) The message bits appear verbatim in the codeword; codebook, decoders and BLER are those of the
+ * plain code, the message BER is about half. Notation: K' = K + crc, A' = order[0 .. K'), mask = its indicator, z = butterfly(u) (the
+ * encoder's stages u[a] ^= u[a + inc] in natural order), coded[i] = z[bitrev(i)], H the CRC matrix, T x = mask & butterfly(x),
+ * syndrome(u)[r] = (sum_j H[r][j] u[order[j]]) ^ u[order[K + r]].
+ *   T^-1     u = x, then `depth` times u = x ^ u ^ T u; depth = the least t >= 1 after which every unit vector of A' is solved
+ *            (1 for every constructed code; at most n).
+ *   parity   the CRC stays a constraint on u, where every decoder checks it, so crc of the K' unfrozen positions of z are not free:
+ *            walking i = K' - 1 .. 0 with p = order[i], D_p = T^-1 e_p and c_p = syndrome(D_p), p is accepted when c_p is linearly
+ *            independent over GF(2) of the accepted columns, until crc are. par_u = the accepted positions in that order, msg_u = A'
+ *            without them in the order of `order`, Q = the accepted columns, n_swapped = the accepted positions outside order[K .. K').
+ *   precode  m[K] -> u_info[K]: x0[msg_u[i]] = m[i]; u = T^-1 x0; zP = Q^-1 syndrome(u); u ^= sum_r zP[r] D_{par_u[r]};
+ *            u_info[i] = u[order[i]]. The systematic codeword is polar_encode(u_info), and coded[bitrev(msg_u[i])] = m[i].
+ *   message  u_info[K] -> m[K]: m[i] = butterfly(u with u[order[i]] = u_info[i], check bits recomputed)[msg_u[i]] — polar_encode
+ *            followed by a gather, valid for ANY u_info (a decoder's output); m differs from the sent message exactly when u_info
+ *            differs from the sent one.
+ * polar_get_sys_info / polar_get_sys_positions: depth, n_swapped, and the coded-row indices pos[i] = bitrev(msg_u[i]) [K],
+ * par[r] = bitrev(par_u[r]) [crc] (any output may be NULL). Host tables only: no device is needed. The tables are built at the
+ * first systematic call of a handle and again after polar_set_crc_matrix.
+ * polar_encode_sys_batch[_dev]: msg [B][K] -> coded [B][N] and / or u_info [B][K] (either may be NULL, not both).
+ * polar_sys_message_batch[_dev]: u_info [R][K] -> msg [R][K], R any row count (the cand [B][L][K] of a list call are B L rows);
+ * msg == u_info (in place) is allowed.
+ * polar_sys_soft_batch[_dev]: soft message outputs from a soft-output decode: msg_llr[b][i] = widen(llr[b][pos[i]]) + ext[b][pos[i]]
+ * (llr [B][N] of `fmt`, ext [B][N] doubles, e.g. polar_decode_scan_batch_dev's; one fp64 addition, +inf passes through).
+ * polar_synth_sys_llr_dev: polar_synth_llr_dev (constellation 0 or POLAR_CONST_BPSK, s_or_snr = polar_snr_sqrt_linear(h, Eb/N0)) or
+ * polar_synth_bicm_llr_dev (POLAR_CONST_ASK*, s_or_snr = the SNR in dB) with the systematic codeword: trial t sends as MESSAGE the
+ * info bits those calls draw for trial t, over the same noise. d_llr [B][N] is required; d_msg [B][K] (the message) and d_u_info
+ * [B][K] (its precoded word, what a decoder's output is compared with) may be NULL.
+ * polar_mc_batch_sys: like polar_mc_batch_list: every ENABLED (L, point) simulates all the trials {t0 + i*stride : i < T} of the
+ * systematic workload with decode_scl_llr at that list size and ADDS to stats[(li*n_e + ie)*POLAR_SY_N + c] (host uint64), counted on
+ * the same decodes.
+ * All kernels are bit-packed (a codeword is N / 64 words in the lanes of a wave; no LDS); the _dev forms are stream-ordered with no
+ * host synchronisation, one launch each (polar_synth_sys_llr_dev: three), and two calls on one handle and one stream need nothing
+ * between them; the first systematic call of a handle uploads the tables. Host forms: copies in, the launch, a wait, the copies out.
+ * POLAR_E_ARG before the device is touched: NULL handle or required pointer, unknown fmt, 16-bit rows at an odd address, unknown
+ * constellation or POLAR_RX_MLC, a list size out of range, negative B / R / T, stride < 1; B = 0 (R = 0, T = 0) is POLAR_OK and
+ * writes nothing. */
+int polar_get_sys_info(polar_code_t *h, int *depth, int *n_swapped);
+int polar_get_sys_positions(polar_code_t *h, uint16_t *pos /*[K]*/, uint16_t *par /*[crc]*/);
+int polar_encode_sys_batch(polar_code_t *h, const uint8_t *msg /*[B][K]*/, long B, uint8_t *coded /*[B][N] or NULL*/,
+                           uint8_t *u_info /*[B][K] or NULL*/);
+int polar_encode_sys_batch_dev(polar_code_t *h, const uint8_t *d_msg, long B, uint8_t *d_coded, uint8_t *d_u_info, void *stream);
+int polar_sys_message_batch(polar_code_t *h, const uint8_t *u_info /*[R][K]*/, long R, uint8_t *msg /*[R][K]*/);
+int polar_sys_message_batch_dev(polar_code_t *h, const uint8_t *d_u_info, long R, uint8_t *d_msg, void *stream);
+int polar_sys_soft_batch(polar_code_t *h, const void *llr, int fmt, const double *ext, long B, double *msg_llr /*[B][K]*/);
+int polar_sys_soft_batch_dev(polar_code_t *h, const void *d_llr, int fmt, const double *d_ext, long B, double *d_msg_llr, void *stream);
+int polar_synth_sys_llr_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double s_or_snr,
+                            double *d_llr, uint8_t *d_msg, uint8_t *d_u_info, void *stream);
+#define POLAR_SY_RUN 0      /* every trial */
+#define POLAR_SY_ERR 1      /* decoded u-domain word differs from the sent one (equally: the recovered message does) */
+#define POLAR_SY_BIT_MSG 2  /* wrong message bits */
+#define POLAR_SY_BIT_U 3    /* wrong u-domain info bits, on the same decodes */
+#define POLAR_SY_N 4
+int polar_mc_batch_sys(polar_code_t *h, int constellation, uint64_t seed, uint64_t t0, long T, long stride, const double *axis,
+                       int n_e, const uint8_t *L, int n_L, const uint8_t *enabled /*[n_L*n_e]*/,
+                       uint64_t *stats /*[n_L*n_e][POLAR_SY_N], ADDED to*/);
+
 /* ---- PolarCode::decode_scl_p1(PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);

@@ -43,6 +43,7 @@ FL_RUN, FL_ERR, FL_UNDET, FL_FIRST, FL_FLIPPED, FL_DECODES, FL_N = 0, 1, 2, 3, 4
 FLIP_MAX = 64
 SN_RUN, SN_ERR, SN_UNDET, SN_ITERS, SN_N = 0, 1, 2, 3, 4     # include/polar_amd.h POLAR_SN_*: columns of the SCAN statistics
 SCAN_MINSUM, SCAN_EARLY_STOP, SCAN_MAX_ITERS = 1, 2, 32      # include/polar_amd.h POLAR_SCAN_*
+SY_RUN, SY_ERR, SY_BIT_MSG, SY_BIT_U, SY_N = 0, 1, 2, 3, 4   # include/polar_amd.h POLAR_SY_*: columns of the systematic statistics
 
 
 def _llr_fmt_code(fmt):
@@ -493,14 +494,108 @@ class PolarCode:
         self._chk(self._L.polar_encode_batch(self._h, _p(info2, _u8p), C.c_long(info2.shape[0]), _p(out, _u8p)))
         return out[0] if single else out
 
+
+    # ---- systematic coding ------------------------------------------------
+    def systematic_info(self):
+        """(depth, n_swapped) of the systematic tables (polar_get_sys_info): the rounds T^-1 takes on this frozen set (1 for every
+        constructed code) and how many parity positions lie outside order[K .. K + crc). Host tables only: no GPU is needed."""
+        d, s = C.c_int(), C.c_int()
+        self._chk(self._L.polar_get_sys_info(self._h, C.byref(d), C.byref(s)))
+        return d.value, s.value
+
+    def systematic_positions(self):
+        """(pos [K], par [crc]) uint16 (polar_get_sys_positions): the coded-row indices that carry the message bits —
+        encode_systematic(m)[0][..., pos] == m — and those of the parity positions. Host tables only."""
+        pos, par = np.zeros(self.K, np.uint16), np.zeros(self.crc_size, np.uint16)
+        self._chk(self._L.polar_get_sys_positions(self._h, _p(pos, _u16p), _p(par, _u16p)))
+        return pos, par
+
+    def encode_systematic(self, msg):
+        """Systematic encoder (polar_encode_sys_batch): msg [..., K] -> (coded [..., N], u_info [..., K]); coded == encode(u_info)
+        and coded[..., pos] == msg with pos of systematic_positions()."""
+        m = np.ascontiguousarray(msg, np.uint8)
+        if m.shape[-1:] != (self.K,):
+            raise PolarError(f"encode_systematic: msg must be [..., {self.K}], got shape {m.shape}")
+        m2 = m.reshape(-1, self.K)
+        coded = np.zeros((m2.shape[0], self.N), np.uint8)
+        u = np.zeros((m2.shape[0], self.K), np.uint8)
+        self._chk(self._L.polar_encode_sys_batch(self._h, _p(m2, _u8p), C.c_long(m2.shape[0]), _p(coded, _u8p), _p(u, _u8p)))
+        return coded.reshape(m.shape[:-1] + (self.N,)), u.reshape(m.shape)
+
+    def systematic_message(self, u_info):
+        """Message recovery (polar_sys_message_batch): u_info [..., K] — a decoder's output, a whole list [B, L, K] — -> msg [..., K]."""
+        u = np.ascontiguousarray(u_info, np.uint8)
+        if u.shape[-1:] != (self.K,):
+            raise PolarError(f"systematic_message: u_info must be [..., {self.K}], got shape {u.shape}")
+        u2 = u.reshape(-1, self.K)
+        out = np.zeros_like(u2)
+        self._chk(self._L.polar_sys_message_batch(self._h, _p(u2, _u8p), C.c_long(u2.shape[0]), _p(out, _u8p)))
+        return out.reshape(u.shape)
+
+    def encode_systematic_dev(self, msg_ptr, B, coded_ptr=0, u_info_ptr=0, stream=None):
+        """Device-resident form (polar_encode_sys_batch_dev): msg uint8 [B, K] -> coded uint8 [B, N] and / or u_info uint8 [B, K]."""
+        self._chk(self._L.polar_encode_sys_batch_dev(self._h, C.c_void_p(msg_ptr), C.c_long(B), C.c_void_p(coded_ptr),
+                                                     C.c_void_p(u_info_ptr), _stream_ptr(stream)))
+
+    def systematic_message_dev(self, u_info_ptr, R, msg_ptr, stream=None):
+        """Device-resident form (polar_sys_message_batch_dev): u_info uint8 [R, K] -> msg uint8 [R, K]; msg_ptr == u_info_ptr is allowed."""
+        self._chk(self._L.polar_sys_message_batch_dev(self._h, C.c_void_p(u_info_ptr), C.c_long(R), C.c_void_p(msg_ptr),
+                                                      _stream_ptr(stream)))
+
+    def systematic_soft(self, llr, ext, fmt=None):
+        """Soft message outputs (polar_sys_soft_batch): msg_llr [B, K] = (widen(llr) + ext)[:, pos], llr [B, N] (or [N]) and `fmt` as
+        decode_scan, ext float64 of the same shape."""
+        code, a = _llr_rows(llr, fmt)
+        a2 = a.reshape(-1, self.N)
+        e = np.ascontiguousarray(ext, np.float64).reshape(-1, self.N)
+        if e.shape != a2.shape:
+            raise PolarError("systematic_soft: llr and ext must have the same shape")
+        out = np.zeros((a2.shape[0], self.K), np.float64)
+        self._chk(self._L.polar_sys_soft_batch(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), _p(e, _dp), C.c_long(a2.shape[0]),
+                                               _p(out, _dp)))
+        return out
+
+    def systematic_soft_dev(self, llr_ptr, fmt, ext_ptr, B, msg_llr_ptr, stream=None):
+        """Device-resident form (polar_sys_soft_batch_dev)."""
+        self._chk(self._L.polar_sys_soft_batch_dev(self._h, C.c_void_p(llr_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_void_p(ext_ptr),
+                                                   C.c_long(B), C.c_void_p(msg_llr_ptr), _stream_ptr(stream)))
+
+    def synth_sys_llr_dev(self, seed, trial0, B, s_or_snr, llr_ptr, msg_ptr=0, u_info_ptr=0, constellation=0, stream=None):
+        """polar_synth_sys_llr_dev: synth_llr_dev (constellation 0: s_or_snr = snr_sqrt_linear(Eb/N0)) or synth_bicm_llr_dev (an ASK
+        constellation: the SNR in dB) with the systematic codeword of the trial's info bits, over the same noise."""
+        self._chk(self._L.polar_synth_sys_llr_dev(self._h, C.c_int(_constellation_id(constellation)), C.c_uint64(seed), C.c_uint64(trial0),
+                                                  C.c_long(B), C.c_double(s_or_snr), C.c_void_p(llr_ptr), C.c_void_p(msg_ptr),
+                                                  C.c_void_p(u_info_ptr), _stream_ptr(stream)))
+
+    def mc_batch_sys(self, seed, t0, T, stride, axis, list_size_vec, enabled, stats, constellation=0):
+        """polar_mc_batch_sys: the trials {t0 + i*stride : i < T} of the systematic workload of every enabled (L, point) ADD to stats,
+        uint64 [len(L), len(axis), 4] = SY_RUN, SY_ERR, SY_BIT_MSG, SY_BIT_U."""
+        Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        self._mc_batch_cells(self._L.polar_mc_batch_sys, seed, t0, T, stride, axis, Ls, enabled, stats, constellation, SY_N, True)
+
+    def systematic_stats(self, axis, list_size_vec, max_runs=1000, max_err=100, seed=0, batch=0, constellation=0):
+        """The systematic code over a sweep: rounds of mc_batch_sys, sized and stopped like list_stats' (_stat_rounds). Returns a dict:
+        `stats` uint64 [len(L), len(axis), 4] (SY_* columns), `bler` = ERR over RUN, and `ber_msg`, `ber_u` = the wrong message bits and
+        the wrong u-domain info bits of the same decodes over K RUN, float64 [len(L), len(axis)]."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        stats = np.zeros((len(Ls), len(ax), SY_N), np.uint64)
+        self._stat_rounds("systematic_stats", lambda t0, T, enabled: self.mc_batch_sys(seed, t0, T, 1, ax, Ls, enabled, stats, constellation),
+                          stats, SY_ERR, SY_RUN, max_runs, max_err, batch)
+        run = np.maximum(stats[:, :, SY_RUN], 1).astype(np.float64)
+        return {"stats": stats, "bler": stats[:, :, SY_ERR] / run, "ber_msg": stats[:, :, SY_BIT_MSG] / (run * self.K),
+                "ber_u": stats[:, :, SY_BIT_U] / (run * self.K)}
+
     # ---- decoders -----------------------------------------------------------------------
-    def decode_scl_llr(self, llr, list_size, out=None, fmt=None):
+    def decode_scl_llr(self, llr, list_size, out=None, fmt=None, systematic=False):
         """PolarCode::decode_scl_llr (PolarCode.cpp:130-148). `llr` is [N] or [B, N]; float32 and float16 arrays travel as
         they are and are widened exactly on the device, anything else is taken as float64. fmt="bf16": `llr` holds bfloat16
         bit patterns as uint16 (numpy has no bfloat16); fmt="f16" takes binary16 patterns as uint16 likewise. The result is
         the float64 call's on the widened values, bit for bit.
         out (optional): a C-contiguous uint8 [B, K] array to receive the bits (a caller that decodes batch after batch keeps
-        one: a fresh 64-MiB array costs its page faults on every call)."""
+        one: a fresh 64-MiB array costs its page faults on every call).
+        systematic=True: the rows carry systematic codewords (encode_systematic); the decoded word goes through the message step
+        (systematic_message, in place in `out`) and the MESSAGE bits are returned."""
         code, a = _llr_rows(llr, fmt)
         single = a.ndim == 1
         a2 = a.reshape(-1, self.N)
@@ -510,6 +605,8 @@ class PolarCode:
             raise PolarError("out must be a C-contiguous uint8 array of shape [B, K]")
         self._chk(self._L.polar_decode_scl_llr_batch_fmt(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(a2.shape[0]),
                                                     C.c_int(list_size), _p(out, _u8p)))
+        if systematic:
+            self._chk(self._L.polar_sys_message_batch(self._h, _p(out, _u8p), C.c_long(a2.shape[0]), _p(out, _u8p)))
         return out[0] if single else out
 
     def decode_scl_llr_list(self, llr, list_size, fmt=None):
@@ -638,12 +735,13 @@ class PolarCode:
             raise PolarError("list size out of range [1, 64] in schedule %r" % (v,))
         return np.array(v, np.uint8)
 
-    def decode_scl_llr_adaptive(self, llr, schedule=(1, 4, 32), fmt=None):
+    def decode_scl_llr_adaptive(self, llr, schedule=(1, 4, 32), fmt=None, systematic=False):
         """Adaptive list decoding (polar_decode_scl_llr_adaptive_batch): every row is decoded with the list sizes of `schedule`
         (strictly increasing, at most 8, each 1 .. 64) in turn until the winner passes the CRC. Returns (out [B, K] uint8, pm [B]
         float64, stage [B] uint8, crc_ok [B] uint8): the word, its metric, the stage that delivered it and whether that stage
         accepted it (0 only at the last stage). out equals decode_scl_llr at the list size schedule[stage]. `llr` and `fmt` as
-        decode_scl_llr_list; a single row [N] is a batch of one. The code needs a CRC."""
+        decode_scl_llr_list; a single row [N] is a batch of one. The code needs a CRC.
+        systematic=True: `out` is the message of the delivered word (systematic_message)."""
         code, a = _llr_rows(llr, fmt)
         a2 = a.reshape(-1, self.N)
         B, Ls = a2.shape[0], self._schedule(schedule)
@@ -654,6 +752,8 @@ class PolarCode:
         self._chk(self._L.polar_decode_scl_llr_adaptive_batch(
             self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), _p(Ls, _u8p), C.c_int(len(Ls)), _p(out, _u8p),
             C.c_void_p(pm.ctypes.data), C.c_void_p(stage.ctypes.data), C.c_void_p(crc_ok.ctypes.data)))
+        if systematic:
+            out = self.systematic_message(out)
         return out, pm, stage, crc_ok
 
     def decode_scl_llr_adaptive_dev(self, llr_ptr, fmt, B, schedule, out_ptr, pm_ptr=0, stage_ptr=0, crc_ok_ptr=0, stream=None):
@@ -689,13 +789,14 @@ class PolarCode:
         return {"stats": stats, "bler": stats[:, AD_ERR] / run, "undetected_rate": stats[:, AD_UNDET] / run, "stage_share": share,
                 "mean_effort": share @ np.cumsum(Ls.astype(np.float64))}
 
-    def decode_sc_flip(self, llr, max_flips=8, fmt=None, return_candidates=False):
+    def decode_sc_flip(self, llr, max_flips=8, fmt=None, return_candidates=False, systematic=False):
         """SC-Flip (polar_decode_sc_flip_batch): one plain SC pass; while the word fails the CRC, whole re-decodes with one decision
         inverted — the `max_flips` (0 .. 64) unfrozen leaves of smallest |LLR| of the first pass, least reliable first. Returns (out
         [B, K] uint8, crc_ok [B] uint8, n_dec [B] uint8, flip [B] int32): the delivered word, whether it passed the CRC, the passes it
         took and the flipped position in decoding order (-1: none). return_candidates=True adds (cand [B, max_flips] int32, mag
         [B, max_flips] float64): pass 0's candidates and their magnitudes (-1 / inf past K + crc). `llr` and `fmt` as
-        decode_scl_llr_list; a single row [N] is a batch of one. The code needs a CRC; n <= 12."""
+        decode_scl_llr_list; a single row [N] is a batch of one. The code needs a CRC; n <= 12.
+        systematic=True: `out` is the message of the delivered word (systematic_message)."""
         code, a = _llr_rows(llr, fmt)
         a2 = a.reshape(-1, self.N)
         B, T = a2.shape[0], int(max_flips)
@@ -709,6 +810,8 @@ class PolarCode:
             self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), C.c_int(T), _p(out, _u8p), C.c_void_p(crc_ok.ctypes.data),
             C.c_void_p(n_dec.ctypes.data), C.c_void_p(flip.ctypes.data), C.c_void_p(cand.ctypes.data if return_candidates else 0),
             C.c_void_p(mag.ctypes.data if return_candidates else 0)))
+        if systematic:
+            out = self.systematic_message(out)
         return (out, crc_ok, n_dec, flip, cand, mag) if return_candidates else (out, crc_ok, n_dec, flip)
 
     def decode_sc_flip_dev(self, llr_ptr, fmt, B, max_flips, out_ptr, crc_ok_ptr=0, n_dec_ptr=0, flip_ptr=0, cand_ptr=0, mag_ptr=0,
@@ -750,14 +853,16 @@ class PolarCode:
             res[name] = stats[:, col] / run
         return res
 
-    def decode_scan(self, llr, iters=4, fmt=None, minsum=False, early_stop=False):
+    def decode_scan(self, llr, iters=4, fmt=None, minsum=False, early_stop=False, systematic=False):
         """SCAN soft-output decoding (polar_decode_scan_batch): the SC schedule with LLRs passed in both directions, `iters` (1 .. 32)
         times. Returns (out [B, K] uint8, info_llr [B, K] float64, ext [B, N] float64, crc_ok [B] uint8, n_iter [B] uint8): the hard
         word, the LLRs of the info bits (out = info_llr < 0), the extrinsic LLRs of the coded bits, indexed like the row (+inf where
         the frozen set alone fixes a bit; a posteriori: llr + ext), whether the decided check bits are the CRC's (1 without a CRC),
         and the iterations that ran. minsum: f(a, b) = sgn sgn min instead of the f-node of decode_scl_llr; early_stop (needs a CRC):
         the first iteration whose decisions pass the CRC is the last. `llr` and `fmt` as decode_scl_llr_list; a single row [N] is a
-        batch of one. Rows must be finite; n <= 11."""
+        batch of one. Rows must be finite; n <= 11.
+        systematic=True: `out` is the message of the hard word (systematic_message) and, in place of info_llr, msg_llr [B, K] =
+        (llr + ext)[:, pos] comes back: the a-posteriori LLRs of the message bits (systematic_soft)."""
         code, a = _llr_rows(llr, fmt)
         a2 = a.reshape(-1, self.N)
         B = a2.shape[0]
@@ -770,6 +875,8 @@ class PolarCode:
             self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(B), C.c_int(iters), C.c_int(_scan_flags(minsum, early_stop)),
             _p(out, _u8p), C.c_void_p(info_llr.ctypes.data), C.c_void_p(ext.ctypes.data), C.c_void_p(crc_ok.ctypes.data),
             C.c_void_p(n_iter.ctypes.data)))
+        if systematic:
+            out, info_llr = self.systematic_message(out), self.systematic_soft(a2, ext, code)
         return out, info_llr, ext, crc_ok, n_iter
 
     def decode_scan_dev(self, llr_ptr, fmt, B, iters, out_ptr, info_llr_ptr=0, ext_ptr=0, crc_ok_ptr=0, n_iter_ptr=0, minsum=False,

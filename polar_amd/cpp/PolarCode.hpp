@@ -299,6 +299,31 @@ public:
         }
         return r;
     }
+    // Systematic coding (polar_encode_sys_batch, polar_sys_message_batch): B messages back to back -> B codewords that
+    // carry them verbatim at systematic_positions(); `u_info` (optional) receives the precoded words, with encode(u_info) == coded.
+    // systematic_message: the messages of B decoded u-domain words (any decoder's output); decode_scl_llr_systematic: both steps.
+    std::vector<uint8_t> encode_systematic(const std::vector<uint8_t> &msg, std::vector<uint8_t> *u_info = nullptr) {
+        need(msg.size() % _info_length == 0, "encode_systematic: size must be a multiple of info_length");
+        const long B = (long)(msg.size() / _info_length);
+        std::vector<uint8_t> coded((size_t)B * _block_length);
+        if (u_info) u_info->assign(msg.size(), 0);
+        if (B) check(polar_encode_sys_batch(_h, msg.data(), B, coded.data(), u_info ? u_info->data() : nullptr));
+        return coded;
+    }
+    std::vector<uint8_t> systematic_message(const std::vector<uint8_t> &u_info) {
+        need(u_info.size() % _info_length == 0, "systematic_message: size must be a multiple of info_length");
+        std::vector<uint8_t> msg(u_info.size());
+        if (!msg.empty()) check(polar_sys_message_batch(_h, u_info.data(), (long)(u_info.size() / _info_length), msg.data()));
+        return msg;
+    }
+    std::vector<uint8_t> decode_scl_llr_systematic(const std::vector<double> &llr, uint16_t list_size) {
+        return systematic_message(decode_scl_llr_batch(llr, list_size));
+    }
+    std::vector<uint16_t> systematic_positions() {
+        std::vector<uint16_t> pos(_info_length);
+        check(polar_get_sys_positions(_h, pos.data(), nullptr));
+        return pos;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").

@@ -394,6 +394,7 @@ void polar_destroy(polar_code_t *h) {
     h->d_slot_n.release();
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
+    sys_release(h);
     h->d_flip_ops.release(); h->d_flip_i32.release(); h->d_scan_ops.release(); h->d_sc_ops.release(); h->d_sc_lat_ops.release(); h->d_flag_words.release(); h->d_var_scr.release(); h->d_tab_scr.release(); h->d_head_rec.release();
     delete h;
 }
@@ -429,6 +430,7 @@ int polar_get_crc_matrix(const polar_code_t *h, uint8_t *m) {
 int polar_set_crc_matrix(polar_code_t *h, const uint8_t *m) {
     if (!h || (!m && h->crc)) return fail(POLAR_E_ARG, "NULL argument");
     drop_clones(h);
+    sys_release(h);                          // (the parity positions of systematic coding depend on the matrix: rebuilt by the next such call)
     if (h->crc) memcpy(h->crcm.data(), m, (size_t)h->crc * h->K);
     int rc = derive_tables(h);
     if (rc) return rc;

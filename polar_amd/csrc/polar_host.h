@@ -11,6 +11,7 @@
 //   polar_adaptive.cpp    adaptive list decoding: a schedule of list sizes, escalated until the CRC passes, and its sweep
 //   polar_flip.cpp        SC-Flip: CRC-aided single-bit retries of SC decoding, and its sweep
 //   polar_scan.cpp        SCAN: soft-output decoding by soft cancellation, and its sweep
+//   polar_sys.cpp         systematic coding: its host tables, precode / message recovery / soft message outputs, its workload and sweep
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction;
 //                         the walk the sweeps of polar_list.cpp and polar_adaptive.cpp share (sweep_begin, sweep_walk)
@@ -222,6 +223,8 @@ struct HostPipe {
     long us_copy_in = 0, us_wait = 0, us_copy_out = 0, us_total = 0;
 };
 
+struct SysTables;
+
 struct polar_code {
     int n = 0, N = 0, K = 0, crc = 0;
     double eps = 0.0;
@@ -283,6 +286,7 @@ struct polar_code {
     DevBuf<int32_t> d_flip_i32;      //   host form and sweep: flip [B] and cand [B][T]
     std::vector<uint32_t> scan_ops;  // SCAN: the walk of scan_kernel (PolarScanParams::ops), built and uploaded by the first call (polar_scan.cpp)
     DevBuf<uint32_t> d_scan_ops;
+    SysTables *sys = nullptr;        // systematic coding: host tables, their device copies and staging, built by the first systematic call and dropped by polar_set_crc_matrix (polar_sys.cpp)
     DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never
@@ -471,7 +475,7 @@ void fill_demap(int cid, int N, double n0, PolarDemapParams &p);
 int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, long B, hipStream_t st, const double **d_llr);
 // polar_montecarlo.cpp — the channel of a sweep point in synth_kernel's parameters: BPSK at an Eb/N0 (constellation 0) or ASK / BICM at an SNR, both in dB
 void fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point);
-// The walk polar_mc_batch_list, polar_mc_batch_adaptive, polar_mc_batch_flip and polar_mc_batch_scan share. A cell: one enabled entry — its point of the axis, its chunk
+// The walk polar_mc_batch_list, polar_mc_batch_adaptive, polar_mc_batch_flip, polar_mc_batch_scan and polar_mc_batch_sys share. A cell: one enabled entry — its point of the axis, its chunk
 // length, its `width` counters at `ctr` in d_mc_ctr and in `stats`
 struct Sweep { polar_code *h; int cid; uint64_t seed, t0; long T, stride; const double *axis; uint64_t *stats; DevGuard dg; };
 struct SweepCell { int point; long chunk; size_t ctr; int width; };
@@ -482,6 +486,8 @@ int sweep_begin(Sweep &sw, polar_code *h, bool ptrs_set, const char *what, int c
 // n_ctr zeroed device counters; per cell and chunk of c trials: synth_kernel into d_in (LLR rows) and d_bytes_a (sent info), then
 // body(cell, c) — the null stream, buffers sized by the caller —; at the end the cells' counters ADD to stats
 int sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, size_t n_ctr, const std::function<int(const SweepCell &, long)> &body);
+// polar_sys.cpp — drops the systematic tables and their device buffers (polar_destroy, polar_set_crc_matrix)
+void sys_release(polar_code *h);
 // polar_hostpipe.cpp
 // rows that are received symbols instead of LLRs (polar_decode_bicm_batch*): M elements per row, demapped on the device
 struct SymRows { int cid, M; double n0; };
