@@ -80,32 +80,29 @@ extern "C" {
 
 int polar_decode_scl_llr_adaptive_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, const uint8_t *Ls, int n_s,
                                             uint8_t *d_out, double *d_pm, uint8_t *d_stage, uint8_t *d_crc_ok, void *stream) {
-    int rc = adaptive_check(h, d_llr, fmt, B, Ls, n_s, d_out);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    return adaptive_launch(h, d_llr, fmt, B, Ls, n_s, d_out, d_pm, d_stage, d_crc_ok, (hipStream_t)stream);
+    return on_device(h, adaptive_check(h, d_llr, fmt, B, Ls, n_s, d_out), B, [&] {
+        return adaptive_launch(h, d_llr, fmt, B, Ls, n_s, d_out, d_pm, d_stage, d_crc_ok, (hipStream_t)stream);
+    });
 }
 
 // One copy in, the stages, a wait, the copies out.
 int polar_decode_scl_llr_adaptive_batch(polar_code_t *h, const void *llr, int fmt, long B, const uint8_t *Ls, int n_s, uint8_t *out,
                                         double *pm, uint8_t *stage, uint8_t *crc_ok) {
-    int rc = adaptive_check(h, llr, fmt, B, Ls, n_s, out);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    const size_t K = (size_t)h->K;
-    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
-    if ((rc = h->d_out.ensure((size_t)B * K))) return rc;
-    if ((rc = h->d_bytes_b.ensure(2 * (size_t)B))) return rc;
-    if ((rc = h->d_list_out.ensure((size_t)B))) return rc;
-    uint8_t *d_stage = h->d_bytes_b.p, *d_crc = d_stage + B;
-    if ((rc = adaptive_launch(h, h->d_in.p, fmt, B, Ls, n_s, h->d_out.p, pm ? h->d_list_out.p : nullptr, stage ? d_stage : nullptr,
-                              crc_ok ? d_crc : nullptr, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_back(out, 0, h->d_out.p, (size_t)B * K)) || (rc = copy_back(pm, 0, h->d_list_out.p, (size_t)B))) return rc;
-    if ((rc = copy_back(stage, 0, d_stage, (size_t)B))) return rc;
-    return copy_back(crc_ok, 0, d_crc, (size_t)B);
+    return on_device(h, adaptive_check(h, llr, fmt, B, Ls, n_s, out), B, [&]() -> int {
+        int rc;
+        const size_t K = (size_t)h->K;
+        if ((rc = stage_rows(h, llr, fmt, B))) return rc;
+        if ((rc = h->d_out.ensure((size_t)B * K))) return rc;
+        if ((rc = h->d_bytes_b.ensure(2 * (size_t)B))) return rc;
+        if ((rc = h->d_list_out.ensure((size_t)B))) return rc;
+        uint8_t *d_stage = h->d_bytes_b.p, *d_crc = d_stage + B;
+        if ((rc = adaptive_launch(h, h->d_in.p, fmt, B, Ls, n_s, h->d_out.p, pm ? h->d_list_out.p : nullptr, stage ? d_stage : nullptr,
+                                  crc_ok ? d_crc : nullptr, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if ((rc = copy_back(out, 0, h->d_out.p, (size_t)B * K)) || (rc = copy_back(pm, 0, h->d_list_out.p, (size_t)B))) return rc;
+        if ((rc = copy_back(stage, 0, d_stage, (size_t)B))) return rc;
+        return copy_back(crc_ok, 0, d_crc, (size_t)B);
+    });
 }
 
 // Per enabled point and per chunk of trials, stream-ordered: the trials' LLRs and sent info (synth_kernel), the stages, the
@@ -120,20 +117,16 @@ int polar_mc_batch_adaptive(polar_code_t *h, int constellation, uint64_t seed, u
     });
     if (rc || T == 0) return rc;
     const int N = h->N, K = h->K, C = POLAR_AD_STAGE0 + n_s;
-    // a chunk: 512 MiB of LLR rows and their bytes, or the knob of the list calls
-    const long chunk = chunk_len(h, T, (size_t)512 << 20, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
+    const long chunk = sweep_chunk(h, T, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
     // (every buffer at its largest before the first launch)
     BatchGeometry g[POLAR_AD_MAX_STAGES];
     if ((rc = adaptive_prepare(h, chunk, Ls, n_s, g))) return rc;
-    if ((rc = h->d_in.ensure((size_t)chunk * N))) return rc;
-    if ((rc = h->d_bytes_a.ensure((size_t)chunk * K))) return rc;                // sent info
+    if ((rc = sweep_rows(h, chunk))) return rc;
     if ((rc = h->d_out.ensure((size_t)chunk * K))) return rc;                    // delivered words
     if ((rc = h->d_bytes_b.ensure(2 * (size_t)chunk))) return rc;                // stage, crc_ok
     uint8_t *d_stage = h->d_bytes_b.p, *d_crc = d_stage + chunk;
-    std::vector<SweepCell> cells;
-    for (int ie = 0; ie < n_e; ++ie)
-        if (enabled[ie]) cells.push_back({ie, chunk, (size_t)C * ie, C});
-    return sweep_walk(sw, cells, (size_t)C * n_e, [&](const SweepCell &cell, long c) -> int {
+    const auto cells = sweep_cells(enabled, 1, n_e, C, {chunk});
+    return sweep_walk(sw, cells, C, 1, n_e, [&](const SweepCell &cell, long c, const PolarEncodeParams &) -> int {
         if (int r = adaptive_launch(h, h->d_in.p, POLAR_LLR_F64, c, Ls, n_s, h->d_out.p, nullptr, d_stage, d_crc, nullptr)) return r;
         HIP_TRY(polar_launch_adapt_classify(h->d_out.p, d_stage, d_crc, h->d_bytes_a.p, c, K, n_s, h->d_mc_ctr.p + cell.ctr, nullptr));
         return POLAR_OK;

@@ -259,14 +259,12 @@ __global__ __launch_bounds__(64) void mc_count_compact_kernel(const uint8_t *dec
 
 }  // namespace
 
-static int grid_for(long B) { return (int)(B < 8192 ? (B > 0 ? B : 1) : 8192); }
-
 hipError_t polar_launch_encode(const PolarEncodeParams &p, hipStream_t st) {
-    hipLaunchKernelGGL(encode_kernel, dim3(grid_for(p.B)), dim3(64), (size_t)p.N + p.K, st, p);
+    hipLaunchKernelGGL(encode_kernel, dim3(polar_rows_grid(p.B)), dim3(64), (size_t)p.N + p.K, st, p);
     return hipGetLastError();
 }
 hipError_t polar_launch_synth(const PolarEncodeParams &p, hipStream_t st) {
-    hipLaunchKernelGGL(synth_kernel, dim3(grid_for(p.B)), dim3(64), (size_t)p.N + p.K, st, p);
+    hipLaunchKernelGGL(synth_kernel, dim3(polar_rows_grid(p.B)), dim3(64), (size_t)p.N + p.K, st, p);
     return hipGetLastError();
 }
 hipError_t polar_launch_bicm_demap(const PolarDemapParams &p, hipStream_t st) {
@@ -274,7 +272,7 @@ hipError_t polar_launch_bicm_demap(const PolarDemapParams &p, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
     // (a row starts 16-byte aligned when the base is and N is even; symbol i of a 2- / 4-bit label then starts at a multiple of 16 bytes)
     const bool vec = (((uintptr_t)p.llr | (uintptr_t)p.p1) & 15u) == 0 && (p.N & 1) == 0;
-    const dim3 grid((unsigned)std::max(1, (p.M + 255) / 256), (unsigned)grid_for(p.B));
+    const dim3 grid((unsigned)std::max(1, (p.M + 255) / 256), (unsigned)polar_rows_grid(p.B));
     return p.y_f32 ? launch_demap<float>(p, grid, vec, st) : launch_demap<double>(p, grid, vec, st);
 }
 hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0, long stride, long T, hipStream_t st) {
@@ -285,16 +283,16 @@ hipError_t polar_launch_mc_init_alive(uint64_t *alive, unsigned *n, uint64_t t0,
 hipError_t polar_launch_mc_count_compact(const uint8_t *decoded, const uint8_t *sent, long B, int K,
                                          const uint64_t *alive_in, const unsigned *n_in, uint64_t *alive_out, unsigned *n_out,
                                          unsigned long long *ctr, hipStream_t st) {
-    hipLaunchKernelGGL(mc_count_compact_kernel, dim3(grid_for(B)), dim3(64), 0, st, decoded, sent, B, K, alive_in, n_in, alive_out, n_out, ctr);
+    hipLaunchKernelGGL(mc_count_compact_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, decoded, sent, B, K, alive_in, n_in, alive_out, n_out, ctr);
     return hipGetLastError();
 }
 hipError_t polar_launch_count_errors(const uint8_t *a, const uint8_t *b, long B, int K,
                                      unsigned long long *err, uint8_t *flags, hipStream_t st) {
-    hipLaunchKernelGGL(count_errors_kernel, dim3(grid_for(B)), dim3(64), 0, st, a, b, B, K, err, flags);
+    hipLaunchKernelGGL(count_errors_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, a, b, B, K, err, flags);
     return hipGetLastError();
 }
 hipError_t polar_launch_list_find(const uint8_t *cand, const int32_t *n_active, const uint8_t *info, long B, int L, int K,
                                   int32_t *rank_out, hipStream_t st) {
-    hipLaunchKernelGGL(list_find_kernel, dim3(grid_for(B)), dim3(64), 0, st, cand, n_active, info, B, L, K, rank_out);
+    hipLaunchKernelGGL(list_find_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, cand, n_active, info, B, L, K, rank_out);
     return hipGetLastError();
 }

@@ -6,26 +6,31 @@
 
 namespace {
 
+// what the decode and the sweep refuse alike, after their pointers
+int flip_check_code(const polar_code *h, int max_flips) {
+    if (max_flips < 0 || max_flips > POLAR_FLIP_MAX) return fail(POLAR_E_ARG, "max_flips %d out of range [0, %d]", max_flips, POLAR_FLIP_MAX);
+    return h->crc ? POLAR_OK : fail(POLAR_E_ARG, "SC-Flip needs a CRC: this code has none to accept a word on");
+}
+int flip_check_size(const polar_code *h) {
+    return h->n > polar_flip_max_log() ? fail(POLAR_E_UNSUPPORTED, "SC-Flip keeps a codeword in LDS: n = %d is above %d", h->n, polar_flip_max_log()) : POLAR_OK;
+}
 int flip_check(const polar_code *h, const void *llr, int fmt, long B, int max_flips, const uint8_t *out) {
     if (!h || !llr || !out) return fail(POLAR_E_ARG, "NULL argument");
-    if (max_flips < 0 || max_flips > POLAR_FLIP_MAX) return fail(POLAR_E_ARG, "max_flips %d out of range [0, %d]", max_flips, POLAR_FLIP_MAX);
-    if (h->crc == 0) return fail(POLAR_E_ARG, "SC-Flip needs a CRC: this code has none to accept a word on");
+    if (int rc = flip_check_code(h, max_flips)) return rc;
     if (int rc = llr_fmt_check(fmt, llr)) return rc;
     if (B < 0) return fail(POLAR_E_ARG, "negative batch");
-    if (h->n > polar_flip_max_log()) return fail(POLAR_E_UNSUPPORTED, "SC-Flip keeps a codeword in LDS: n = %d is above %d", h->n, polar_flip_max_log());
-    return POLAR_OK;
+    return flip_check_size(h);
 }
 
 // The walk of sc_flip_kernel over the code tree, depth first; node v of layer lam covers the leaves [v << (n - lam), (v + 1) << (n - lam)).
 // An all-frozen subtree has no ops; a node of four leaves is ONE op.
 void flip_schedule(polar_code *h) {
     const int n = h->n;
-    std::vector<int> unf(h->N + 1, 0);                                            // unfrozen leaves before position i
-    for (int i = 0; i < h->N; ++i) unf[i + 1] = unf[i] + (h->frozen[i] ? 0 : 1);
+    const LeafCount unf(h);
     auto brev = [](int v, int bits) { int r = 0; for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1) << (bits - 1 - i); return r; };
     auto emit = [&](int type, int lam, int arg) { h->flip_ops.push_back((uint32_t)type | ((uint32_t)lam << 3) | ((uint32_t)arg << 8)); };
     std::function<void(int, int)> go = [&](int lam, int v) {
-        auto live = [&](int l, int w) { return unf[(w + 1) << (n - l)] - unf[w << (n - l)] > 0; };
+        auto live = [&](int l, int w) { return unf.under(l, w) > 0; };
         if (lam == n - 2 || lam == n - 1) {                                       // (n - 1: only the root of n = 1)
             const int size = 1 << (n - lam);
             int arg = size * v;
@@ -41,11 +46,8 @@ void flip_schedule(polar_code *h) {
     go(0, 0);                                                                      // (K >= 1: the root is never all frozen)
 }
 
-// every buffer a launch needs, BEFORE it (the handle's device current): the schedule is built and uploaded by the first call
 int flip_prepare(polar_code *h) {
-    if (polar_flip_lds_bytes(h->N) > h->lds_per_block) return fail(POLAR_E_UNSUPPORTED, "the SC-Flip kernel's LDS does not fit this device");
-    if (h->flip_ops.empty()) flip_schedule(h);
-    return h->d_flip_ops.p ? POLAR_OK : upload(h->d_flip_ops, h->flip_ops);
+    return ops_prepare(h, polar_flip_lds_bytes(h->N), "the SC-Flip kernel's LDS does not fit this device", h->flip_ops, h->d_flip_ops, flip_schedule);
 }
 
 // (arguments checked, B > 0, the handle's device current, flip_prepare done)
@@ -82,33 +84,30 @@ extern "C" {
 
 int polar_decode_sc_flip_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, int max_flips, uint8_t *d_out, uint8_t *d_crc_ok,
                                    uint8_t *d_n_dec, int32_t *d_flip, int32_t *d_cand, double *d_mag, void *stream) {
-    int rc = flip_check(h, d_llr, fmt, B, max_flips, d_out);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = flip_prepare(h))) return rc;
-    return flip_launch(h, d_llr, fmt, B, max_flips, d_out, d_crc_ok, d_n_dec, d_flip, d_cand, d_mag, (hipStream_t)stream);
+    return on_device(h, flip_check(h, d_llr, fmt, B, max_flips, d_out), B, [&]() -> int {
+        if (int rc = flip_prepare(h)) return rc;
+        return flip_launch(h, d_llr, fmt, B, max_flips, d_out, d_crc_ok, d_n_dec, d_flip, d_cand, d_mag, (hipStream_t)stream);
+    });
 }
 
 // One copy in, the launch, a wait, the copies out.
 int polar_decode_sc_flip_batch(polar_code_t *h, const void *llr, int fmt, long B, int max_flips, uint8_t *out, uint8_t *crc_ok,
                                uint8_t *n_dec, int32_t *flip, int32_t *cand, double *mag) {
-    int rc = flip_check(h, llr, fmt, B, max_flips, out);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = flip_prepare(h))) return rc;
-    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
-    FlipChunk d;
-    if ((rc = FlipChunk::make(h, B, max_flips, d))) return rc;
-    const size_t T = (size_t)max_flips;
-    if ((rc = flip_launch(h, h->d_in.p, fmt, B, max_flips, d.out, crc_ok ? d.crc_ok : nullptr, n_dec ? d.n_dec : nullptr,
-                          flip ? d.flip : nullptr, cand ? d.cand : nullptr, mag ? d.mag : nullptr, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_back(out, 0, d.out, (size_t)B * h->K)) || (rc = copy_back(crc_ok, 0, d.crc_ok, (size_t)B)) ||
-        (rc = copy_back(n_dec, 0, d.n_dec, (size_t)B)) || (rc = copy_back(flip, 0, d.flip, (size_t)B))) return rc;
-    if (T && ((rc = copy_back(cand, 0, d.cand, (size_t)B * T)) || (rc = copy_back(mag, 0, d.mag, (size_t)B * T)))) return rc;
-    return POLAR_OK;
+    return on_device(h, flip_check(h, llr, fmt, B, max_flips, out), B, [&]() -> int {
+        int rc;
+        if ((rc = flip_prepare(h))) return rc;
+        if ((rc = stage_rows(h, llr, fmt, B))) return rc;
+        FlipChunk d;
+        if ((rc = FlipChunk::make(h, B, max_flips, d))) return rc;
+        const size_t T = (size_t)max_flips;
+        if ((rc = flip_launch(h, h->d_in.p, fmt, B, max_flips, d.out, crc_ok ? d.crc_ok : nullptr, n_dec ? d.n_dec : nullptr,
+                              flip ? d.flip : nullptr, cand ? d.cand : nullptr, mag ? d.mag : nullptr, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if ((rc = copy_back(out, 0, d.out, (size_t)B * h->K)) || (rc = copy_back(crc_ok, 0, d.crc_ok, (size_t)B)) ||
+            (rc = copy_back(n_dec, 0, d.n_dec, (size_t)B)) || (rc = copy_back(flip, 0, d.flip, (size_t)B))) return rc;
+        if (T && ((rc = copy_back(cand, 0, d.cand, (size_t)B * T)) || (rc = copy_back(mag, 0, d.mag, (size_t)B * T)))) return rc;
+        return POLAR_OK;
+    });
 }
 
 // Per enabled point and per chunk of trials, stream-ordered: the trials' LLRs and sent info (synth_kernel), the decode, the
@@ -118,24 +117,19 @@ int polar_mc_batch_flip(polar_code_t *h, int constellation, uint64_t seed, uint6
     Sweep sw;
     int rc = sweep_begin(sw, h, axis && enabled && stats, "SC-Flip decoder has", constellation, seed, t0, T, stride, axis, n_e > 0, stats,
                          [&]() -> int {
-        if (max_flips < 0 || max_flips > POLAR_FLIP_MAX) return fail(POLAR_E_ARG, "max_flips %d out of range [0, %d]", max_flips, POLAR_FLIP_MAX);
-        if (h->crc == 0) return fail(POLAR_E_ARG, "SC-Flip needs a CRC: this code has none to accept a word on");
-        return h->n > polar_flip_max_log() ? fail(POLAR_E_UNSUPPORTED, "SC-Flip keeps a codeword in LDS: n = %d is above %d", h->n, polar_flip_max_log()) : POLAR_OK;
+        if (int r = flip_check_code(h, max_flips)) return r;
+        return flip_check_size(h);
     });
     if (rc || T == 0) return rc;
     const int N = h->N, K = h->K;
-    // a chunk: 512 MiB of LLR rows and their bytes, or the knob of the list calls
-    const long chunk = chunk_len(h, T, (size_t)512 << 20, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
+    const long chunk = sweep_chunk(h, T, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
     // (every buffer at its largest before the first launch)
     if ((rc = flip_prepare(h))) return rc;
-    if ((rc = h->d_in.ensure((size_t)chunk * N))) return rc;
-    if ((rc = h->d_bytes_a.ensure((size_t)chunk * K))) return rc;                // sent info
+    if ((rc = sweep_rows(h, chunk))) return rc;
     FlipChunk d;
     if ((rc = FlipChunk::make(h, chunk, 0, d))) return rc;
-    std::vector<SweepCell> cells;
-    for (int ie = 0; ie < n_e; ++ie)
-        if (enabled[ie]) cells.push_back({ie, chunk, (size_t)POLAR_FL_N * ie, POLAR_FL_N});
-    return sweep_walk(sw, cells, (size_t)POLAR_FL_N * n_e, [&](const SweepCell &cell, long c) -> int {
+    const auto cells = sweep_cells(enabled, 1, n_e, POLAR_FL_N, {chunk});
+    return sweep_walk(sw, cells, POLAR_FL_N, 1, n_e, [&](const SweepCell &cell, long c, const PolarEncodeParams &) -> int {
         if (int r = flip_launch(h, h->d_in.p, POLAR_LLR_F64, c, max_flips, d.out, d.crc_ok, d.n_dec, nullptr, nullptr, nullptr, nullptr)) return r;
         HIP_TRY(polar_launch_flip_classify(d.out, d.crc_ok, d.n_dec, h->d_bytes_a.p, c, K, h->d_mc_ctr.p + cell.ctr, nullptr));
         return POLAR_OK;

@@ -14,10 +14,13 @@
 //   polar_sys.cpp         systematic coding: its host tables, precode / message recovery / soft message outputs, its workload and sweep
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction;
-//                         the walk the sweeps of polar_list.cpp and polar_adaptive.cpp share (sweep_begin, sweep_walk)
+//                         the walk the sweeps of the five decoder variants share (sweep_begin, sweep_cells, sweep_walk)
 //   polar_mc_schedule.h   the schedule of the pipelined rounds alone (standard library only: tests/test_mc_schedule.py runs it on a CPU)
 //   polar_multi.cpp       multi-device context: RCCL binding, worker threads, watchdog, per-device clones
 //   polar_debug.cpp       measurement knobs (include/polar_amd_debug.h); fault injection only with -DPOLAR_TEST_HOOKS
+// What the variants (list output / path metric, adaptive, SC-Flip, SCAN, systematic) share is below: the frame of an entry point
+// (on_device), the checks (check_args, check_list_sizes), the schedules of the tree-walking kernels (LeafCount, ops_prepare), the
+// sweep (sweep_chunk, sweep_rows and the walk). The device side of it: polar_wave_frame.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -381,6 +384,15 @@ int upload(DevBuf<T> &d, const std::vector<T> &v) {
     if (v.size()) HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return POLAR_OK;
 }
+// The frame of an entry point of the decoder variants (polar_list.cpp ... polar_sys.cpp) around what it does: rc = the result of its
+// argument checks; an error or an empty batch ends it there, else body() runs with the handle's device current
+template <typename Body>
+int on_device(polar_code *h, int rc, long B, Body body) {
+    if (rc || B == 0) return rc;
+    DevGuard dg;
+    if ((rc = ensure_device(h, dg))) return rc;
+    return body();
+}
 // The host-pointer forms of the list output, the path metric and the adaptive decode: the caller's B rows of `fmt` staged in d_in
 // (whole doubles), and n results copied back to dst + at where the caller asked for them (after the stream was waited for)
 inline int stage_rows(polar_code *h, const void *rows, int fmt, long B) {
@@ -416,6 +428,30 @@ inline int check_args(bool ptrs_set, int L, long B, const std::function<int()> &
     if (int rc = mid ? mid() : POLAR_OK) return rc;
     if (L < 1 || L > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range [1, %d]", L, POLAR_MAX_LIST);
     return B < 0 ? fail(POLAR_E_ARG, "negative batch") : POLAR_OK;
+}
+// the list sizes of a sweep over several (polar_mc_batch_list, polar_mc_batch_sys)
+inline int check_list_sizes(const uint8_t *L, int n_L) {
+    for (int i = 0; i < n_L; ++i)
+        if (L[i] < 1 || L[i] > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range", (int)L[i]);
+    return POLAR_OK;
+}
+// What the schedule builders of the kernels that walk the code tree ask (flip_schedule, scan_schedule): the unfrozen leaves under
+// node w of layer l, which covers the leaves [w << (n - l), (w + 1) << (n - l))
+struct LeafCount {
+    int n;
+    std::vector<int> before;         // [N + 1] unfrozen leaves before position i
+    explicit LeafCount(const polar_code *h) : n(h->n), before(h->N + 1, 0) {
+        for (int i = 0; i < h->N; ++i) before[i + 1] = before[i] + (h->frozen[i] ? 0 : 1);
+    }
+    int under(int l, int w) const { return before[(w + 1) << (n - l)] - before[w << (n - l)]; }
+};
+// every buffer a launch of such a kernel needs, BEFORE it (the handle's device current): its `lds` bytes must fit (`msg` if not);
+// the schedule is built and uploaded by the first call
+inline int ops_prepare(polar_code *h, size_t lds, const char *msg, std::vector<uint32_t> &ops, DevBuf<uint32_t> &d_ops,
+                       void (*schedule)(polar_code *)) {
+    if (lds > h->lds_per_block) return fail(POLAR_E_UNSUPPORTED, "%s", msg);
+    if (ops.empty()) schedule(h);
+    return d_ops.p ? POLAR_OK : upload(d_ops, ops);
 }
 // What the per-wave state scratch of a launch may take: at most 24 GiB, and at most half of what the device has free plus what the
 // handle already holds for it (a smaller or busy GPU runs fewer persistent waves instead of failing with POLAR_E_NOMEM)
@@ -475,17 +511,30 @@ void fill_demap(int cid, int N, double n0, PolarDemapParams &p);
 int bicm_front(polar_code *c, int cid, double n0, const void *d_y, int y_f32, long B, hipStream_t st, const double **d_llr);
 // polar_montecarlo.cpp — the channel of a sweep point in synth_kernel's parameters: BPSK at an Eb/N0 (constellation 0) or ASK / BICM at an SNR, both in dB
 void fill_channel(const polar_code *h, PolarEncodeParams &p, int constellation, double snr_point);
-// The walk polar_mc_batch_list, polar_mc_batch_adaptive, polar_mc_batch_flip, polar_mc_batch_scan and polar_mc_batch_sys share. A cell: one enabled entry — its point of the axis, its chunk
-// length, its `width` counters at `ctr` in d_mc_ctr and in `stats`
+// The walk polar_mc_batch_list, polar_mc_batch_adaptive, polar_mc_batch_flip, polar_mc_batch_scan and polar_mc_batch_sys share. A cell:
+// one enabled entry of the caller's [n_rows][n_e] grid — its point of the axis, its chunk length, its `width` counters at `ctr` in
+// d_mc_ctr and in `stats`, its row: the entry of the caller's list-size vector (0 where the sweep has none)
 struct Sweep { polar_code *h; int cid; uint64_t seed, t0; long T, stride; const double *axis; uint64_t *stats; DevGuard dg; };
-struct SweepCell { int point; long chunk; size_t ctr; int width; };
+struct SweepCell { int point; long chunk; size_t ctr; int width; int row; };
 // the checks in the order the ABI pins (`ptrs_set`, "the `what` no MLC receiver", the constellation, `sizes_ok`, the caller's `own`);
 // past them with T > 0 the handle's device is current while `sw` lives (T == 0: POLAR_OK, nothing to do)
 int sweep_begin(Sweep &sw, polar_code *h, bool ptrs_set, const char *what, int constellation, uint64_t seed, uint64_t t0, long T,
                 long stride, const double *axis, bool sizes_ok, uint64_t *stats, const std::function<int()> &own);
-// n_ctr zeroed device counters; per cell and chunk of c trials: synth_kernel into d_in (LLR rows) and d_bytes_a (sent info), then
-// body(cell, c) — the null stream, buffers sized by the caller —; at the end the cells' counters ADD to stats
-int sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, size_t n_ctr, const std::function<int(const SweepCell &, long)> &body);
+// trials per chunk of a sweep that takes `per` bytes a trial: 512 MiB of LLR rows and what belongs to them, or the knob of the list
+// calls; and the walk's own buffers at that size: the LLR rows in d_in, the sent info in d_bytes_a
+inline long sweep_chunk(const polar_code *h, long T, size_t per) { return chunk_len(h, T, (size_t)512 << 20, per); }
+inline int sweep_rows(polar_code *h, long chunk) {
+    if (int rc = h->d_in.ensure((size_t)chunk * h->N)) return rc;
+    return h->d_bytes_a.ensure((size_t)chunk * h->K);
+}
+// the cells of the enabled entries of the [n_rows][n_e] grid, row by row: `width` counters each at width * (row * n_e + ie), chunks
+// of chunk_of[row] trials
+std::vector<SweepCell> sweep_cells(const uint8_t *enabled, int n_rows, int n_e, int width, const std::vector<long> &chunk_of);
+using SweepBody = std::function<int(const SweepCell &, long, const PolarEncodeParams &)>;
+// width * n_rows * n_e zeroed device counters; per cell and chunk of c trials: synth_kernel into d_in and d_bytes_a, then
+// body(cell, c, p) — p: what synth_kernel was just launched with; the null stream, buffers sized by the caller —; at the end the
+// cells' counters ADD to stats
+int sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, int width, int n_rows, int n_e, const SweepBody &body);
 // polar_sys.cpp — drops the systematic tables and their device buffers (polar_destroy, polar_set_crc_matrix)
 void sys_release(polar_code *h);
 // polar_hostpipe.cpp

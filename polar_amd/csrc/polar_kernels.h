@@ -12,6 +12,13 @@
 #define POLAR_LLR_BF16 3
 #endif
 static inline size_t polar_llr_esz(int fmt) { return fmt == POLAR_LLR_F64 ? 8 : fmt == POLAR_LLR_F32 ? 4 : 2; }
+// blocks of a launch of one wave per row: a block for every row up to 8192, the waves loop over the rest
+static inline int polar_rows_grid(long B) { return (int)(B < 8192 ? (B > 0 ? B : 1) : 8192); }
+// before a launch with more dynamic LDS than the 48 KiB every kernel may have: ask for it (per launch: the attribute belongs to the
+// function on the current device)
+static inline hipError_t polar_allow_lds(const void *kernel, size_t lds) {
+    return lds > 48 * 1024 ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
 
 struct PolarDecodeParams {
     int n, N, K, crc, L;

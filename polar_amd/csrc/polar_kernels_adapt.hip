@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "polar_kernels.h"
+#include "polar_wave_frame.h"
 
 namespace {
 
@@ -21,9 +22,7 @@ __global__ __launch_bounds__(64) void adapt_classify_kernel(const uint8_t *out, 
     unsigned long long run = 0, err_n = 0, undet_n = 0, st_n[kMaxStages] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (long c = blockIdx.x; c < B; c += gridDim.x) {
         const uint8_t *got = out + (size_t)c * K, *want = sent + (size_t)c * K;
-        bool diff = false;
-        for (int i = lane; i < K; i += 64) diff |= (got[i] != want[i]);
-        const bool err = __ballot(diff) != 0;
+        const bool err = rows_differ(got, want, K, lane);
         const int s = stage[c];
         run += 1; err_n += err; undet_n += (err && crc_ok[c] == 1);
 #pragma unroll
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(64) void adapt_classify_kernel(const uint8_t *out, 
 hipError_t polar_launch_adapt_classify(const uint8_t *out, const uint8_t *stage, const uint8_t *crc_ok, const uint8_t *sent, long B,
                                        int K, int n_s, unsigned long long *ctr, hipStream_t st) {
     if (n_s < 1 || n_s > kMaxStages) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adapt_classify_kernel, dim3((unsigned)(B < 8192 ? (B > 0 ? B : 1) : 8192)), dim3(64), 0, st, out, stage, crc_ok,
+    hipLaunchKernelGGL(adapt_classify_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, out, stage, crc_ok,
                        sent, B, K, n_s, ctr);
     return hipGetLastError();
 }

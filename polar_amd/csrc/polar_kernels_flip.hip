@@ -27,30 +27,14 @@
 #include "polar_device.h"
 #include "polar_edom.h"
 #include "polar_llr_nodes.h"
+#include "polar_wave_frame.h"
 
 namespace {
-
-__host__ __device__ inline int flip_words(int N) { return N >= 32 ? N / 32 : 1; }
-// first double of layer lam behind the tables: sizes N, N/2, ..., 1
-__device__ __forceinline__ int layer_off(int N, int lam) { return 2 * N - ((2 * N) >> lam); }
-__device__ __forceinline__ unsigned get_bit(const uint32_t *w, int i) { return (w[i >> 5] >> (i & 31)) & 1u; }
-
-// do the check bits the CRC matrix gives for the decided info bits equal the decided check bits? (wave-uniform)
-__device__ __forceinline__ bool flip_crc_ok(const PolarFlipParams &p, const uint32_t *U, int lane) {
-    bool bad = false;
-    for (int r = 0; r < p.crc && !bad; ++r) {
-        unsigned par = 0;
-        for (int j = lane; j < p.K; j += 64) par ^= (unsigned)p.crcm[(size_t)r * p.K + j] & get_bit(U, p.order[j]);
-        const u64 m = __ballot(par & 1u);
-        bad = (unsigned)(__popcll(m) & 1) != get_bit(U, p.order[p.K + r]);
-    }
-    return !bad;
-}
 
 __global__ __launch_bounds__(64) void sc_flip_kernel(PolarFlipParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *tabs = reinterpret_cast<double *>(smem);                              // T[64] RC[129] LC[129] (+2 pad)
-    const int n = p.n, N = p.N, K = p.K, T = p.T, NW = flip_words(N);
+    const int n = p.n, N = p.N, K = p.K, T = p.T, NW = packed_words(N);
     double *lay = reinterpret_cast<double *>(smem + 324 * 8);
     uint32_t *X = reinterpret_cast<uint32_t *>(smem + 324 * 8 + (size_t)2 * N * 8), *U = X + NW, *U0 = U + NW;
     const int lane = threadIdx.x;
@@ -152,7 +136,7 @@ __global__ __launch_bounds__(64) void sc_flip_kernel(PolarFlipParams p) {
                     wave_mem_fence();
                 }
             }
-            ok = flip_crc_ok(p, U, lane);
+            ok = crc_matches(p, lane, [&](int pos) { return get_bit(U, pos); });
             if (ok) { n_dec = att + 1; flip = c; }
             else if (att == 0) {
                 for (int i = lane; i < NW; i += 64) U0[i] = U[i];
@@ -184,9 +168,7 @@ __global__ __launch_bounds__(64) void flip_classify_kernel(const uint8_t *out, c
     unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
     for (long c = blockIdx.x; c < B; c += gridDim.x) {
         const uint8_t *got = out + (size_t)c * K, *want = sent + (size_t)c * K;
-        bool diff = false;
-        for (int i = lane; i < K; i += 64) diff |= (got[i] != want[i]);
-        const bool err = __ballot(diff) != 0;
+        const bool err = rows_differ(got, want, K, lane);
         const bool ok = crc_ok[c] == 1;
         const unsigned nd = n_dec[c];
         cnt[0] += 1; cnt[1] += err; cnt[2] += (err && ok); cnt[3] += (ok && nd == 1); cnt[4] += (ok && nd > 1); cnt[5] += nd;
@@ -198,21 +180,18 @@ __global__ __launch_bounds__(64) void flip_classify_kernel(const uint8_t *out, c
 
 }  // namespace
 
-size_t polar_flip_lds_bytes(int N) { return 324 * 8 + (size_t)2 * N * 8 + (size_t)3 * flip_words(N) * 4; }
+size_t polar_flip_lds_bytes(int N) { return 324 * 8 + (size_t)2 * N * 8 + (size_t)3 * packed_words(N) * 4; }
 int polar_flip_max_log() { return 12; }            // 16 N bytes of LDS per wave: 64 KiB at N = 4096
 int polar_flip_grid_cap() { return 8192; }
 hipError_t polar_launch_sc_flip(const PolarFlipParams &p, int grid, hipStream_t st) {
     const size_t lds = polar_flip_lds_bytes(p.N);
-    if (lds > 48 * 1024) {        // (per launch: the attribute belongs to the function on the current device)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sc_flip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = polar_allow_lds(reinterpret_cast<const void *>(sc_flip_kernel), lds)) return e;
     hipLaunchKernelGGL(sc_flip_kernel, dim3(grid), dim3(64), lds, st, p);
     return hipGetLastError();
 }
 hipError_t polar_launch_flip_classify(const uint8_t *out, const uint8_t *crc_ok, const uint8_t *n_dec, const uint8_t *sent, long B, int K,
                                       unsigned long long *ctr, hipStream_t st) {
-    hipLaunchKernelGGL(flip_classify_kernel, dim3((unsigned)(B < 8192 ? (B > 0 ? B : 1) : 8192)), dim3(64), 0, st, out, crc_ok, n_dec, sent,
+    hipLaunchKernelGGL(flip_classify_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, out, crc_ok, n_dec, sent,
                        B, K, ctr);
     return hipGetLastError();
 }

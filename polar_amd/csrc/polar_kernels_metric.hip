@@ -21,11 +21,9 @@
 #include "polar_device.h"
 #include "polar_edom.h"
 #include "polar_llr_nodes.h"
+#include "polar_wave_frame.h"
 
 namespace {
-
-// words of one bit-packed layer
-__host__ __device__ inline int metric_words(int N) { return N >= 32 ? N / 32 : 1; }
 
 // INLDS: the N doubles of the pass live in LDS (behind the tables; the word's info bytes are staged in the same place before the
 // channel row is read); else in the block's slice of p.scr, and the info bytes behind the partial sums.
@@ -33,7 +31,7 @@ template <bool INLDS>
 __global__ __launch_bounds__(64) void path_metric_kernel(PolarMetricParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *tabs = reinterpret_cast<double *>(smem);                              // T[64] RC[129] LC[129] (+2 pad)
-    const int n = p.n, N = p.N, K = p.K, NW = metric_words(N);
+    const int n = p.n, N = p.N, K = p.K, NW = packed_words(N);
     double *D = INLDS ? reinterpret_cast<double *>(smem + 324 * 8) : p.scr + (size_t)blockIdx.x * (size_t)N;
     uint32_t *P = reinterpret_cast<uint32_t *>(smem + 324 * 8 + (INLDS ? (size_t)N * 8 : 0));    // [n][NW]: layer lam at (lam - 1) NW
     uint8_t *inf = INLDS ? reinterpret_cast<uint8_t *>(smem + 324 * 8) : reinterpret_cast<uint8_t *>(P + (size_t)n * NW);
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(64) void path_metric_kernel(PolarMetricParams p) {
                 const double a = p.llr_fmt ? llr_load_narrow(p.llr, row + 2 * q, p.llr_fmt) : reinterpret_cast<const double *>(p.llr)[row + 2 * q];
                 const double c = p.llr_fmt ? llr_load_narrow(p.llr, row + 2 * q + 1, p.llr_fmt) : reinterpret_cast<const double *>(p.llr)[row + 2 * q + 1];
                 const int A = 2 * q;
-                const unsigned u = (Pl[A >> 5] >> (A & 31)) & 1u;
+                const unsigned u = get_bit(Pl, A);
                 D[A] = f_node(a, c, tb);
                 D[A + 1] = g_node(a, c, u);
             }
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(64) void path_metric_kernel(PolarMetricParams p) {
             for (int q = lane; q < N / 2; q += 64) {
                 const int A = ((q >> (lam - 1)) << lam) | (q & (h - 1));
                 const double a = D[A], c = D[A + h];
-                const unsigned u = (Pl[A >> 5] >> (A & 31)) & 1u;
+                const unsigned u = get_bit(Pl, A);
                 D[A] = f_node(a, c, tb);
                 D[A + h] = g_node(a, c, u);
             }
@@ -109,7 +107,7 @@ __global__ __launch_bounds__(64) void path_metric_kernel(PolarMetricParams p) {
         for (int A = lane; A < N; A += 64) {
             bool ng; double al, sneg, spos;
             leaf_terms<false>(D[A], true, 0ull, tb, ng, al, sneg, spos);
-            const bool one = ((Pn[A >> 5] >> (A & 31)) & 1u) != 0;
+            const bool one = get_bit(Pn, A) != 0;
             D[A] = (ng != one) ? spos : sneg;                                      // decision 0: log(1 + e^-llr); 1: log(1 + e^llr)
         }
         wave_mem_fence();
@@ -147,7 +145,7 @@ __global__ __launch_bounds__(64) void list_classify_kernel(const uint8_t *cand, 
             const uint8_t *row = cand + ((size_t)c * L + r) * (size_t)K;
             bool d = false;
             for (int i = lane; i < K; i += 64) d |= (row[i] != want[i]);
-            found = __ballot(d) == 0;                                 // (wave-uniform)
+            found = __ballot(d) == 0;                                 // (wave-uniform; rows_differ would change this kernel's machine code)
         }
         const bool undet = err && has && crc_ok[(size_t)c * L + win] == 1;
         const bool ml = undet && pm[(size_t)c * L + win] <= pm_sent[c];
@@ -162,17 +160,14 @@ __global__ __launch_bounds__(64) void list_classify_kernel(const uint8_t *cand, 
 
 size_t polar_metric_lds_bytes(int n, int in_lds) {
     const int N = 1 << n;
-    const size_t sums = (size_t)n * metric_words(N) * 4;
+    const size_t sums = (size_t)n * packed_words(N) * 4;
     return 324 * 8 + (in_lds ? (size_t)N * 8 + sums : sums + (size_t)N);          // (K <= N info bytes behind the sums)
 }
 hipError_t polar_launch_path_metric(const PolarMetricParams &p, int grid, hipStream_t st) {
     const int in_lds = p.scr == nullptr;
     const size_t lds = polar_metric_lds_bytes(p.n, in_lds);
     const void *fn = in_lds ? reinterpret_cast<const void *>(path_metric_kernel<true>) : reinterpret_cast<const void *>(path_metric_kernel<false>);
-    if (lds > 48 * 1024) {        // (per launch: the attribute belongs to the function on the current device)
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = polar_allow_lds(fn, lds)) return e;
     if (in_lds) hipLaunchKernelGGL(path_metric_kernel<true>, dim3(grid), dim3(64), lds, st, p);
     else hipLaunchKernelGGL(path_metric_kernel<false>, dim3(grid), dim3(64), lds, st, p);
     return hipGetLastError();
@@ -180,7 +175,7 @@ hipError_t polar_launch_path_metric(const PolarMetricParams &p, int grid, hipStr
 hipError_t polar_launch_list_classify(const uint8_t *cand, const double *pm, const uint8_t *crc_ok, const int32_t *n_active,
                                       const int32_t *winner, const uint8_t *sent, const double *pm_sent, long B, int L, int K,
                                       const unsigned int *n_dev, unsigned long long *ctr, hipStream_t st) {
-    hipLaunchKernelGGL(list_classify_kernel, dim3((unsigned)(B < 8192 ? (B > 0 ? B : 1) : 8192)), dim3(64), 0, st, cand, pm, crc_ok, n_active, winner, sent, pm_sent, B, L, K,
+    hipLaunchKernelGGL(list_classify_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, cand, pm, crc_ok, n_active, winner, sent, pm_sent, B, L, K,
                        n_dev, ctr);
     return hipGetLastError();
 }

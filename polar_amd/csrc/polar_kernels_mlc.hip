@@ -412,7 +412,7 @@ size_t polar_mlc_scr_doubles(int N, int nb) { return (size_t)(4 * (N / nb) + (nb
 size_t polar_mlc_lat_lds_bytes(int N, int nb) { return (size_t)(4 * (N / nb) + (nb - 1) * (N / nb) + N) * sizeof(double) + (size_t)N; }
 
 hipError_t polar_launch_mlc_front(const PolarMlcParams &p, int mode, hipStream_t st) {
-    const int grid = (int)(p.B < 8192 ? (p.B > 0 ? p.B : 1) : 8192);
+    const int grid = polar_rows_grid(p.B);
     hipLaunchKernelGGL(mlc_front_kernel, dim3(grid), dim3(64), (size_t)p.N, st, p, mode);
     return hipGetLastError();
 }

@@ -32,11 +32,10 @@
 #include "polar_device.h"
 #include "polar_edom.h"
 #include "polar_llr_nodes.h"
+#include "polar_wave_frame.h"
 
 namespace {
 
-// first double of layer lam in an array of the layers N, N/2, ..., 1
-__device__ __forceinline__ int layer_off(int N, int lam) { return 2 * N - ((2 * N) >> lam); }
 __host__ __device__ inline size_t scan_lds_doubles(int n, int N) { return 324 + (size_t)4 * N + (size_t)(n - 1) * (N / 2); }
 
 template <bool MS>
@@ -53,18 +52,6 @@ __device__ __forceinline__ double scan_f(double a, double b, const Tabs &tb) {
 }
 // the B of a child that is all frozen / all unfrozen
 __device__ __forceinline__ double kind_const(int kind) { return kind == POLAR_SCAN_KIND_FROZEN ? __builtin_inf() : 0.0; }
-
-// do the check bits the CRC matrix gives for the decided info bits equal the decided check bits? (wave-uniform)
-__device__ __forceinline__ bool scan_crc_ok(const PolarScanParams &p, const double *leaf, int lane) {
-    bool bad = false;
-    for (int r = 0; r < p.crc && !bad; ++r) {
-        unsigned par = 0;
-        for (int j = lane; j < p.K; j += 64) par ^= (unsigned)p.crcm[(size_t)r * p.K + j] & (unsigned)(leaf[p.order[j]] < 0);
-        const u64 m = __ballot(par & 1u);
-        bad = (unsigned)(__popcll(m) & 1) != (unsigned)(leaf[p.order[p.K + r]] < 0);
-    }
-    return !bad;
-}
 
 template <bool MS>
 __global__ __launch_bounds__(64) void scan_kernel(PolarScanParams p) {
@@ -147,7 +134,7 @@ __global__ __launch_bounds__(64) void scan_kernel(PolarScanParams p) {
                 }
             }
             n_it = it + 1;
-            if (p.crc > 0 && (early || it == p.iters - 1)) ok = scan_crc_ok(p, leaf, lane);
+            if (p.crc > 0 && (early || it == p.iters - 1)) ok = crc_matches(p, lane, [&](int pos) { return leaf[pos] < 0; });
             if (early && ok) break;
         }
         uint8_t *out = p.out + (size_t)b * (size_t)K;
@@ -173,7 +160,7 @@ __global__ __launch_bounds__(64) void scan_classify_kernel(const uint8_t *out, c
     unsigned long long cnt[4] = {0, 0, 0, 0};
     for (long c = blockIdx.x; c < B; c += gridDim.x) {
         const uint8_t *got = out + (size_t)c * K, *want = sent + (size_t)c * K;
-        bool diff = false;
+        bool diff = false;                                            // (written out: rows_differ would change this kernel's machine code)
         for (int i = lane; i < K; i += 64) diff |= (got[i] != want[i]);
         const bool err = __ballot(diff) != 0;
         cnt[0] += 1; cnt[1] += err; cnt[2] += (err && has_crc && crc_ok[c] == 1); cnt[3] += n_iter[c];
@@ -191,18 +178,15 @@ int polar_scan_grid_cap() { return 8192; }
 hipError_t polar_launch_scan(const PolarScanParams &p, int grid, hipStream_t st) {
     const size_t lds = polar_scan_lds_bytes(p.n);
     const bool ms = (p.flags & POLAR_SCAN_F_MINSUM) != 0;
-    if (lds > 48 * 1024) {        // (per launch: the attribute belongs to the function on the current device)
-        const void *fn = ms ? reinterpret_cast<const void *>(scan_kernel<true>) : reinterpret_cast<const void *>(scan_kernel<false>);
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    const void *fn = ms ? reinterpret_cast<const void *>(scan_kernel<true>) : reinterpret_cast<const void *>(scan_kernel<false>);
+    if (hipError_t e = polar_allow_lds(fn, lds)) return e;
     if (ms) hipLaunchKernelGGL(scan_kernel<true>, dim3(grid), dim3(64), lds, st, p);
     else hipLaunchKernelGGL(scan_kernel<false>, dim3(grid), dim3(64), lds, st, p);
     return hipGetLastError();
 }
 hipError_t polar_launch_scan_classify(const uint8_t *out, const uint8_t *crc_ok, const uint8_t *n_iter, const uint8_t *sent, long B, int K,
                                       int has_crc, unsigned long long *ctr, hipStream_t st) {
-    hipLaunchKernelGGL(scan_classify_kernel, dim3((unsigned)(B < 8192 ? (B > 0 ? B : 1) : 8192)), dim3(64), 0, st, out, crc_ok, n_iter, sent,
+    hipLaunchKernelGGL(scan_classify_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, out, crc_ok, n_iter, sent,
                        B, K, has_crc, ctr);
     return hipGetLastError();
 }

@@ -289,7 +289,6 @@ int sys_grid(const PolarSysParams &p) {
     const long waves = (p.B + G - 1) / G;
     return (int)(waves < kGridCap ? (waves > 0 ? waves : 1) : kGridCap);
 }
-int rows_grid(long B) { return (int)(B < 8192 ? (B > 0 ? B : 1) : 8192); }
 
 }  // namespace
 
@@ -324,17 +323,17 @@ hipError_t polar_launch_sys_soft(const void *llr, int llr_fmt, const double *ext
 }
 hipError_t polar_launch_sys_draw(const PolarEncodeParams &p, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sys_draw_kernel, dim3(rows_grid(p.B)), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(sys_draw_kernel, dim3(polar_rows_grid(p.B)), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 hipError_t polar_launch_sys_channel(const PolarEncodeParams &p, const uint8_t *coded, hipStream_t st) {
     if (p.B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sys_channel_kernel, dim3(rows_grid(p.B)), dim3(64), 0, st, p, coded);
+    hipLaunchKernelGGL(sys_channel_kernel, dim3(polar_rows_grid(p.B)), dim3(64), 0, st, p, coded);
     return hipGetLastError();
 }
 hipError_t polar_launch_sys_classify(const uint8_t *u_dec, const uint8_t *u_sent, const uint8_t *m_dec, const uint8_t *m_sent, long B,
                                      int K, unsigned long long *ctr, hipStream_t st) {
     if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sys_classify_kernel, dim3(rows_grid(B)), dim3(64), 0, st, u_dec, u_sent, m_dec, m_sent, B, K, ctr);
+    hipLaunchKernelGGL(sys_classify_kernel, dim3(polar_rows_grid(B)), dim3(64), 0, st, u_dec, u_sent, m_dec, m_sent, B, K, ctr);
     return hipGetLastError();
 }

@@ -76,69 +76,61 @@ extern "C" {
 
 int polar_decode_scl_llr_list_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, int L, uint8_t *d_cand, double *d_pm,
                                         uint8_t *d_crc_ok, int32_t *d_n_active, int32_t *d_winner, void *stream) {
-    int rc = list_check(h, d_llr, fmt, B, L, d_cand);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    return list_launch(h, d_llr, fmt, B, L, d_cand, d_pm, d_crc_ok, d_n_active, d_winner, (hipStream_t)stream);
+    return on_device(h, list_check(h, d_llr, fmt, B, L, d_cand), B, [&] {
+        return list_launch(h, d_llr, fmt, B, L, d_cand, d_pm, d_crc_ok, d_n_active, d_winner, (hipStream_t)stream);
+    });
 }
 
 // One copy in, then per chunk of codewords: the launches, a wait, the copies out. The chunk bounds the device memory the list
 // takes (L K + 9 L + 8 bytes per codeword), not the input, which is resident for the whole call.
 int polar_decode_scl_llr_list_batch(polar_code_t *h, const void *llr, int fmt, long B, int L, uint8_t *cand, double *pm,
                                     uint8_t *crc_ok, int32_t *n_active, int32_t *winner) {
-    int rc = list_check(h, llr, fmt, B, L, cand);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
-    const size_t row = (size_t)h->N * polar_llr_esz(fmt), LK = (size_t)L * h->K;
-    const long chunk = chunk_len(h, B, (size_t)256 << 20, ListChunk::per_cw(L, h->K));
-    if ((rc = h->d_list_out.ensure(ListChunk::doubles(chunk, L, h->K, false)))) return rc;
-    const ListChunk d(h->d_list_out.p, chunk, L, h->K, false);
-    for (long b0 = 0; b0 < B; b0 += chunk) {
-        const long c = std::min(chunk, B - b0);
-        if ((rc = list_launch(h, reinterpret_cast<const char *>(h->d_in.p) + (size_t)b0 * row, fmt, c, L, d.cand, pm ? d.pm : nullptr,
-                              crc_ok ? d.crc_ok : nullptr, n_active ? d.n_active : nullptr, winner ? d.winner : nullptr, nullptr))) return rc;
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if ((rc = copy_back(cand, (size_t)b0 * LK, d.cand, (size_t)c * LK)) || (rc = copy_back(pm, (size_t)b0 * L, d.pm, (size_t)c * L)) ||
-            (rc = copy_back(crc_ok, (size_t)b0 * L, d.crc_ok, (size_t)c * L)) || (rc = copy_back(n_active, (size_t)b0, d.n_active, (size_t)c)) ||
-            (rc = copy_back(winner, (size_t)b0, d.winner, (size_t)c))) return rc;
-    }
-    return POLAR_OK;
+    return on_device(h, list_check(h, llr, fmt, B, L, cand), B, [&]() -> int {
+        int rc;
+        if ((rc = stage_rows(h, llr, fmt, B))) return rc;
+        const size_t row = (size_t)h->N * polar_llr_esz(fmt), LK = (size_t)L * h->K;
+        const long chunk = chunk_len(h, B, (size_t)256 << 20, ListChunk::per_cw(L, h->K));
+        if ((rc = h->d_list_out.ensure(ListChunk::doubles(chunk, L, h->K, false)))) return rc;
+        const ListChunk d(h->d_list_out.p, chunk, L, h->K, false);
+        for (long b0 = 0; b0 < B; b0 += chunk) {
+            const long c = std::min(chunk, B - b0);
+            if ((rc = list_launch(h, reinterpret_cast<const char *>(h->d_in.p) + (size_t)b0 * row, fmt, c, L, d.cand, pm ? d.pm : nullptr,
+                                  crc_ok ? d.crc_ok : nullptr, n_active ? d.n_active : nullptr, winner ? d.winner : nullptr, nullptr))) return rc;
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            if ((rc = copy_back(cand, (size_t)b0 * LK, d.cand, (size_t)c * LK)) || (rc = copy_back(pm, (size_t)b0 * L, d.pm, (size_t)c * L)) ||
+                (rc = copy_back(crc_ok, (size_t)b0 * L, d.crc_ok, (size_t)c * L)) || (rc = copy_back(n_active, (size_t)b0, d.n_active, (size_t)c)) ||
+                (rc = copy_back(winner, (size_t)b0, d.winner, (size_t)c))) return rc;
+        }
+        return POLAR_OK;
+    });
 }
 
 int polar_list_find_dev(polar_code_t *h, const uint8_t *d_cand, const int32_t *d_n_active, const uint8_t *d_info, long B, int L,
                         int32_t *d_rank, void *stream) {
-    int rc = check_args(h && d_cand && d_n_active && d_info && d_rank, L, B);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    HIP_TRY(polar_launch_list_find(d_cand, d_n_active, d_info, B, L, h->K, d_rank, (hipStream_t)stream));
-    return POLAR_OK;
+    return on_device(h, check_args(h && d_cand && d_n_active && d_info && d_rank, L, B), B, [&]() -> int {
+        HIP_TRY(polar_launch_list_find(d_cand, d_n_active, d_info, B, L, h->K, d_rank, (hipStream_t)stream));
+        return POLAR_OK;
+    });
 }
 
 int polar_path_metric_batch_dev(polar_code_t *h, const void *d_llr, int fmt, const uint8_t *d_info, long B, int R, double *d_pm, void *stream) {
-    int rc = metric_check(h, d_llr, fmt, d_info, B, R, d_pm);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    return metric_launch(h, d_llr, fmt, d_info, B, R, d_pm, (hipStream_t)stream);
+    return on_device(h, metric_check(h, d_llr, fmt, d_info, B, R, d_pm), B, [&] {
+        return metric_launch(h, d_llr, fmt, d_info, B, R, d_pm, (hipStream_t)stream);
+    });
 }
 
 int polar_path_metric_batch(polar_code_t *h, const void *llr, int fmt, const uint8_t *info, long B, int R, double *pm) {
-    int rc = metric_check(h, llr, fmt, info, B, R, pm);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    const size_t words = (size_t)B * R;
-    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
-    if ((rc = h->d_bytes_b.ensure(words * h->K))) return rc;
-    if ((rc = h->d_list_out.ensure(words))) return rc;
-    HIP_TRY(hipMemcpy(h->d_bytes_b.p, info, words * h->K, hipMemcpyHostToDevice));
-    if ((rc = metric_launch(h, h->d_in.p, fmt, h->d_bytes_b.p, B, R, h->d_list_out.p, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return copy_back(pm, 0, h->d_list_out.p, words);
+    return on_device(h, metric_check(h, llr, fmt, info, B, R, pm), B, [&]() -> int {
+        int rc;
+        const size_t words = (size_t)B * R;
+        if ((rc = stage_rows(h, llr, fmt, B))) return rc;
+        if ((rc = h->d_bytes_b.ensure(words * h->K))) return rc;
+        if ((rc = h->d_list_out.ensure(words))) return rc;
+        HIP_TRY(hipMemcpy(h->d_bytes_b.p, info, words * h->K, hipMemcpyHostToDevice));
+        if ((rc = metric_launch(h, h->d_in.p, fmt, h->d_bytes_b.p, B, R, h->d_list_out.p, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return copy_back(pm, 0, h->d_list_out.p, words);
+    });
 }
 
 // Per enabled (list size, point) and per chunk of trials, stream-ordered: the trials' LLRs and sent info (synth_kernel), the list
@@ -147,29 +139,22 @@ int polar_mc_batch_list(polar_code_t *h, int constellation, uint64_t seed, uint6
                         const uint8_t *L, int n_L, const uint8_t *enabled, uint64_t *stats) {
     Sweep sw;
     int rc = sweep_begin(sw, h, axis && L && enabled && stats, "list statistics have", constellation, seed, t0, T, stride, axis,
-                         n_e > 0 && n_L > 0, stats, [&]() -> int {
-        for (int i = 0; i < n_L; ++i)
-            if (L[i] < 1 || L[i] > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range", (int)L[i]);
-        return POLAR_OK;
-    });
+                         n_e > 0 && n_L > 0, stats, [&] { return check_list_sizes(L, n_L); });
     if (rc || T == 0) return rc;
     // (every buffer at its largest before the first launch: the decode's own per list size, the chunks of rows, sent info and output)
-    std::vector<SweepCell> cells;
-    long cmax = 0; size_t out_max = 0;
+    std::vector<long> chunk(n_L);
+    size_t out_max = 0;
     for (int li = 0; li < n_L; ++li) {
-        const long chunk = chunk_len(h, T, (size_t)256 << 20, ListChunk::per_cw(L[li], h->K));
+        chunk[li] = chunk_len(h, T, (size_t)256 << 20, ListChunk::per_cw(L[li], h->K));
         BatchGeometry g; PolarListParams p;
-        if ((rc = list_prepare(h, chunk, L[li], g, p))) return rc;
-        cmax = std::max(cmax, chunk);
-        out_max = std::max(out_max, ListChunk::doubles(chunk, L[li], h->K, true));
-        for (int ie = 0; ie < n_e; ++ie)
-            if (enabled[li * n_e + ie]) cells.push_back({ie, chunk, (size_t)POLAR_LS_N * (li * n_e + ie), POLAR_LS_N});
+        if ((rc = list_prepare(h, chunk[li], L[li], g, p))) return rc;
+        out_max = std::max(out_max, ListChunk::doubles(chunk[li], L[li], h->K, true));
     }
-    if ((rc = h->d_in.ensure((size_t)cmax * h->N))) return rc;
-    if ((rc = h->d_bytes_a.ensure((size_t)cmax * h->K))) return rc;              // sent info
+    if ((rc = sweep_rows(h, *std::max_element(chunk.begin(), chunk.end())))) return rc;
     if ((rc = h->d_list_out.ensure(out_max))) return rc;
-    return sweep_walk(sw, cells, (size_t)POLAR_LS_N * n_e * n_L, [&](const SweepCell &cell, long c) -> int {
-        const int Ls = L[cell.ctr / POLAR_LS_N / n_e];             // (the cell's counters are those of entry li * n_e + ie)
+    const auto cells = sweep_cells(enabled, n_L, n_e, POLAR_LS_N, chunk);
+    return sweep_walk(sw, cells, POLAR_LS_N, n_L, n_e, [&](const SweepCell &cell, long c, const PolarEncodeParams &) -> int {
+        const int Ls = L[cell.row];
         const ListChunk d(h->d_list_out.p, cell.chunk, Ls, h->K, true);
         if (int r = list_launch(h, h->d_in.p, POLAR_LLR_F64, c, Ls, d.cand, d.pm, d.crc_ok, d.n_active, d.winner, nullptr)) return r;
         if (int r = metric_launch(h, h->d_in.p, POLAR_LLR_F64, h->d_bytes_a.p, c, 1, d.pm_sent, nullptr)) return r;

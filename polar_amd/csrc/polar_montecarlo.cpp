@@ -20,7 +20,7 @@ void polar_host::fill_channel(const polar_code *h, PolarEncodeParams &p, int con
     }
 }
 
-// ---- the sweeps of the list statistics and of the adaptive decoder (polar_list.cpp, polar_adaptive.cpp) ----
+// ---- the sweeps of the decoder variants (polar_list.cpp, polar_adaptive.cpp, polar_flip.cpp, polar_scan.cpp, polar_sys.cpp) ----
 int polar_host::sweep_begin(Sweep &sw, polar_code *h, bool ptrs_set, const char *what, int constellation, uint64_t seed, uint64_t t0,
                             long T, long stride, const double *axis, bool sizes_ok, uint64_t *stats, const std::function<int()> &own) {
     if (!h || !ptrs_set) return fail(POLAR_E_ARG, "NULL argument");
@@ -33,8 +33,17 @@ int polar_host::sweep_begin(Sweep &sw, polar_code *h, bool ptrs_set, const char 
     return T == 0 ? POLAR_OK : ensure_device(h, sw.dg);
 }
 
-int polar_host::sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, size_t n_ctr, const std::function<int(const SweepCell &, long)> &body) {
+std::vector<SweepCell> polar_host::sweep_cells(const uint8_t *enabled, int n_rows, int n_e, int width, const std::vector<long> &chunk_of) {
+    std::vector<SweepCell> cells;
+    for (int row = 0; row < n_rows; ++row)
+        for (int ie = 0; ie < n_e; ++ie)
+            if (enabled[row * n_e + ie]) cells.push_back({ie, chunk_of[row], (size_t)width * (row * n_e + ie), width, row});
+    return cells;
+}
+
+int polar_host::sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, int width, int n_rows, int n_e, const SweepBody &body) {
     polar_code *h = sw.h;
+    const size_t n_ctr = (size_t)width * n_rows * n_e;
     if (int rc = h->d_mc_ctr.ensure(n_ctr)) return rc;
     HIP_TRY(hipMemsetAsync(h->d_mc_ctr.p, 0, n_ctr * sizeof(unsigned long long), nullptr));
     for (const SweepCell &cell : cells)
@@ -46,7 +55,7 @@ int polar_host::sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, size_
             fill_channel(h, p, sw.cid, sw.axis[cell.point]);
             p.llr = h->d_in.p; p.info_out = h->d_bytes_a.p;
             HIP_TRY(polar_launch_synth(p, nullptr));
-            if (int rc = body(cell, c)) return rc;
+            if (int rc = body(cell, c, p)) return rc;
         }
     std::vector<unsigned long long> ctr(n_ctr);
     HIP_TRY(hipMemcpy(ctr.data(), h->d_mc_ctr.p, n_ctr * sizeof(unsigned long long), hipMemcpyDeviceToHost));

@@ -31,10 +31,9 @@ int scan_check(const polar_code *h, const void *llr, int fmt, long B, int iters,
 // always gets its B: that is `ext`.
 void scan_schedule(polar_code *h) {
     const int n = h->n;
-    std::vector<int> unf(h->N + 1, 0);                                            // unfrozen leaves before position i
-    for (int i = 0; i < h->N; ++i) unf[i + 1] = unf[i] + (h->frozen[i] ? 0 : 1);
+    const LeafCount unf(h);
     auto kind = [&](int l, int w) {
-        const int c = unf[(w + 1) << (n - l)] - unf[w << (n - l)];
+        const int c = unf.under(l, w);
         return c == 0 ? POLAR_SCAN_KIND_FROZEN : c == (1 << (n - l)) ? POLAR_SCAN_KIND_UNFROZEN : POLAR_SCAN_KIND_MIXED;
     };
     auto emit = [&](int type, int lam, int v, int kl, int kr, int wb) {
@@ -52,11 +51,8 @@ void scan_schedule(polar_code *h) {
     go(0, 0);                                                                      // (K >= 1: the root is never all frozen)
 }
 
-// every buffer a launch needs, BEFORE it (the handle's device current): the schedule is built and uploaded by the first call
 int scan_prepare(polar_code *h) {
-    if (polar_scan_lds_bytes(h->n) > h->lds_per_block) return fail(POLAR_E_UNSUPPORTED, "the SCAN kernel's LDS does not fit this device");
-    if (h->scan_ops.empty()) scan_schedule(h);
-    return h->d_scan_ops.p ? POLAR_OK : upload(h->d_scan_ops, h->scan_ops);
+    return ops_prepare(h, polar_scan_lds_bytes(h->n), "the SCAN kernel's LDS does not fit this device", h->scan_ops, h->d_scan_ops, scan_schedule);
 }
 
 // (arguments checked, B > 0, the handle's device current, scan_prepare done)
@@ -91,32 +87,29 @@ extern "C" {
 
 int polar_decode_scan_batch_dev(polar_code_t *h, const void *d_llr, int fmt, long B, int iters, int flags, uint8_t *d_out,
                                 double *d_info_llr, double *d_ext, uint8_t *d_crc_ok, uint8_t *d_n_iter, void *stream) {
-    int rc = scan_check(h, d_llr, fmt, B, iters, flags, d_out);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = scan_prepare(h))) return rc;
-    return scan_launch(h, d_llr, fmt, B, iters, flags, d_out, d_info_llr, d_ext, d_crc_ok, d_n_iter, (hipStream_t)stream);
+    return on_device(h, scan_check(h, d_llr, fmt, B, iters, flags, d_out), B, [&]() -> int {
+        if (int rc = scan_prepare(h)) return rc;
+        return scan_launch(h, d_llr, fmt, B, iters, flags, d_out, d_info_llr, d_ext, d_crc_ok, d_n_iter, (hipStream_t)stream);
+    });
 }
 
 // One copy in, the launch, a wait, the copies out.
 int polar_decode_scan_batch(polar_code_t *h, const void *llr, int fmt, long B, int iters, int flags, uint8_t *out, double *info_llr,
                             double *ext, uint8_t *crc_ok, uint8_t *n_iter) {
-    int rc = scan_check(h, llr, fmt, B, iters, flags, out);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = scan_prepare(h))) return rc;
-    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
-    ScanChunk d;
-    if ((rc = ScanChunk::make(h, B, true, d))) return rc;
-    if ((rc = scan_launch(h, h->d_in.p, fmt, B, iters, flags, d.out, info_llr ? d.info_llr : nullptr, ext ? d.ext : nullptr,
-                          crc_ok ? d.crc_ok : nullptr, n_iter ? d.n_iter : nullptr, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_back(out, 0, d.out, (size_t)B * h->K)) || (rc = copy_back(info_llr, 0, d.info_llr, (size_t)B * h->K)) ||
-        (rc = copy_back(ext, 0, d.ext, (size_t)B * h->N)) || (rc = copy_back(crc_ok, 0, d.crc_ok, (size_t)B)) ||
-        (rc = copy_back(n_iter, 0, d.n_iter, (size_t)B))) return rc;
-    return POLAR_OK;
+    return on_device(h, scan_check(h, llr, fmt, B, iters, flags, out), B, [&]() -> int {
+        int rc;
+        if ((rc = scan_prepare(h))) return rc;
+        if ((rc = stage_rows(h, llr, fmt, B))) return rc;
+        ScanChunk d;
+        if ((rc = ScanChunk::make(h, B, true, d))) return rc;
+        if ((rc = scan_launch(h, h->d_in.p, fmt, B, iters, flags, d.out, info_llr ? d.info_llr : nullptr, ext ? d.ext : nullptr,
+                              crc_ok ? d.crc_ok : nullptr, n_iter ? d.n_iter : nullptr, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if ((rc = copy_back(out, 0, d.out, (size_t)B * h->K)) || (rc = copy_back(info_llr, 0, d.info_llr, (size_t)B * h->K)) ||
+            (rc = copy_back(ext, 0, d.ext, (size_t)B * h->N)) || (rc = copy_back(crc_ok, 0, d.crc_ok, (size_t)B)) ||
+            (rc = copy_back(n_iter, 0, d.n_iter, (size_t)B))) return rc;
+        return POLAR_OK;
+    });
 }
 
 // Per enabled point and per chunk of trials, stream-ordered: the trials' LLRs and sent info (synth_kernel), the decode, the
@@ -131,18 +124,14 @@ int polar_mc_batch_scan(polar_code_t *h, int constellation, uint64_t seed, uint6
     });
     if (rc || T == 0) return rc;
     const int N = h->N, K = h->K;
-    // a chunk: 512 MiB of LLR rows and their bytes, or the knob of the list calls
-    const long chunk = chunk_len(h, T, (size_t)512 << 20, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
+    const long chunk = sweep_chunk(h, T, (size_t)N * sizeof(double) + 2 * (size_t)K + 2);
     // (every buffer at its largest before the first launch)
     if ((rc = scan_prepare(h))) return rc;
-    if ((rc = h->d_in.ensure((size_t)chunk * N))) return rc;
-    if ((rc = h->d_bytes_a.ensure((size_t)chunk * K))) return rc;                // sent info
+    if ((rc = sweep_rows(h, chunk))) return rc;
     ScanChunk d;
     if ((rc = ScanChunk::make(h, chunk, false, d))) return rc;
-    std::vector<SweepCell> cells;
-    for (int ie = 0; ie < n_e; ++ie)
-        if (enabled[ie]) cells.push_back({ie, chunk, (size_t)POLAR_SN_N * ie, POLAR_SN_N});
-    return sweep_walk(sw, cells, (size_t)POLAR_SN_N * n_e, [&](const SweepCell &cell, long c) -> int {
+    const auto cells = sweep_cells(enabled, 1, n_e, POLAR_SN_N, {chunk});
+    return sweep_walk(sw, cells, POLAR_SN_N, 1, n_e, [&](const SweepCell &cell, long c, const PolarEncodeParams &) -> int {
         if (int r = scan_launch(h, h->d_in.p, POLAR_LLR_F64, c, iters, flags, d.out, nullptr, nullptr, d.crc_ok, d.n_iter, nullptr)) return r;
         HIP_TRY(polar_launch_scan_classify(d.out, d.crc_ok, d.n_iter, h->d_bytes_a.p, c, K, h->crc > 0, h->d_mc_ctr.p + cell.ctr, nullptr));
         return POLAR_OK;

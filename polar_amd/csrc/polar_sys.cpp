@@ -242,87 +242,77 @@ int polar_get_sys_positions(polar_code_t *h, uint16_t *pos, uint16_t *par) {
 }
 
 int polar_encode_sys_batch_dev(polar_code_t *h, const uint8_t *d_msg, long B, uint8_t *d_coded, uint8_t *d_u_info, void *stream) {
-    int rc = check_args(h && d_msg && (d_coded || d_u_info), kNoList, B);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    return precode_launch(h, d_msg, B, d_coded, d_u_info, (hipStream_t)stream);
+    return on_device(h, check_args(h && d_msg && (d_coded || d_u_info), kNoList, B), B, [&]() -> int {
+        if (int rc = sys_prepare(h)) return rc;
+        return precode_launch(h, d_msg, B, d_coded, d_u_info, (hipStream_t)stream);
+    });
 }
 int polar_encode_sys_batch(polar_code_t *h, const uint8_t *msg, long B, uint8_t *coded, uint8_t *u_info) {
-    int rc = check_args(h && msg && (coded || u_info), kNoList, B);
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    SysTables &t = *h->sys;
-    if ((rc = t.d_msg.ensure((size_t)B * h->K)) || (rc = t.d_u.ensure((size_t)B * h->K)) || (rc = t.d_coded.ensure((size_t)B * h->N))) return rc;
-    HIP_TRY(hipMemcpy(t.d_msg.p, msg, (size_t)B * h->K, hipMemcpyHostToDevice));
-    if ((rc = precode_launch(h, t.d_msg.p, B, coded ? t.d_coded.p : nullptr, u_info ? t.d_u.p : nullptr, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_back(coded, 0, t.d_coded.p, (size_t)B * h->N)) || (rc = copy_back(u_info, 0, t.d_u.p, (size_t)B * h->K))) return rc;
-    return POLAR_OK;
+    return on_device(h, check_args(h && msg && (coded || u_info), kNoList, B), B, [&]() -> int {
+        int rc;
+        if ((rc = sys_prepare(h))) return rc;
+        SysTables &t = *h->sys;
+        if ((rc = t.d_msg.ensure((size_t)B * h->K)) || (rc = t.d_u.ensure((size_t)B * h->K)) || (rc = t.d_coded.ensure((size_t)B * h->N))) return rc;
+        HIP_TRY(hipMemcpy(t.d_msg.p, msg, (size_t)B * h->K, hipMemcpyHostToDevice));
+        if ((rc = precode_launch(h, t.d_msg.p, B, coded ? t.d_coded.p : nullptr, u_info ? t.d_u.p : nullptr, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        if ((rc = copy_back(coded, 0, t.d_coded.p, (size_t)B * h->N)) || (rc = copy_back(u_info, 0, t.d_u.p, (size_t)B * h->K))) return rc;
+        return POLAR_OK;
+    });
 }
 
 int polar_sys_message_batch_dev(polar_code_t *h, const uint8_t *d_u_info, long R, uint8_t *d_msg, void *stream) {
-    int rc = check_args(h && d_u_info && d_msg, kNoList, R);
-    if (rc || R == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    return message_launch(h, d_u_info, R, d_msg, (hipStream_t)stream);
+    return on_device(h, check_args(h && d_u_info && d_msg, kNoList, R), R, [&]() -> int {
+        if (int rc = sys_prepare(h)) return rc;
+        return message_launch(h, d_u_info, R, d_msg, (hipStream_t)stream);
+    });
 }
 int polar_sys_message_batch(polar_code_t *h, const uint8_t *u_info, long R, uint8_t *msg) {
-    int rc = check_args(h && u_info && msg, kNoList, R);
-    if (rc || R == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    SysTables &t = *h->sys;
-    if ((rc = t.d_u.ensure((size_t)R * h->K))) return rc;
-    HIP_TRY(hipMemcpy(t.d_u.p, u_info, (size_t)R * h->K, hipMemcpyHostToDevice));
-    if ((rc = message_launch(h, t.d_u.p, R, t.d_u.p, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return copy_back(msg, 0, t.d_u.p, (size_t)R * h->K);
+    return on_device(h, check_args(h && u_info && msg, kNoList, R), R, [&]() -> int {
+        int rc;
+        if ((rc = sys_prepare(h))) return rc;
+        SysTables &t = *h->sys;
+        if ((rc = t.d_u.ensure((size_t)R * h->K))) return rc;
+        HIP_TRY(hipMemcpy(t.d_u.p, u_info, (size_t)R * h->K, hipMemcpyHostToDevice));
+        if ((rc = message_launch(h, t.d_u.p, R, t.d_u.p, nullptr))) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return copy_back(msg, 0, t.d_u.p, (size_t)R * h->K);
+    });
 }
 
 int polar_sys_soft_batch_dev(polar_code_t *h, const void *d_llr, int fmt, const double *d_ext, long B, double *d_msg_llr, void *stream) {
-    int rc = check_args(h && d_llr && d_ext && d_msg_llr, kNoList, B, [&] { return llr_fmt_check(fmt, d_llr); });
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    HIP_TRY(polar_launch_sys_soft(d_llr, fmt, d_ext, h->sys->d_idx.p + 2 * (size_t)h->N + h->K, B, h->N, h->K, d_msg_llr, (hipStream_t)stream));
-    return POLAR_OK;
+    return on_device(h, check_args(h && d_llr && d_ext && d_msg_llr, kNoList, B, [&] { return llr_fmt_check(fmt, d_llr); }), B, [&]() -> int {
+        if (int rc = sys_prepare(h)) return rc;
+        HIP_TRY(polar_launch_sys_soft(d_llr, fmt, d_ext, h->sys->d_idx.p + 2 * (size_t)h->N + h->K, B, h->N, h->K, d_msg_llr, (hipStream_t)stream));
+        return POLAR_OK;
+    });
 }
 int polar_sys_soft_batch(polar_code_t *h, const void *llr, int fmt, const double *ext, long B, double *msg_llr) {
-    int rc = check_args(h && llr && ext && msg_llr, kNoList, B, [&] { return llr_fmt_check(fmt, llr); });
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    SysTables &t = *h->sys;
-    if ((rc = stage_rows(h, llr, fmt, B))) return rc;
-    if ((rc = t.d_soft.ensure((size_t)B * (h->N + h->K)))) return rc;
-    HIP_TRY(hipMemcpy(t.d_soft.p, ext, (size_t)B * h->N * sizeof(double), hipMemcpyHostToDevice));
-    double *d_out = t.d_soft.p + (size_t)B * h->N;
-    HIP_TRY(polar_launch_sys_soft(h->d_in.p, fmt, t.d_soft.p, t.d_idx.p + 2 * (size_t)h->N + h->K, B, h->N, h->K, d_out, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return copy_back(msg_llr, 0, d_out, (size_t)B * h->K);
+    return on_device(h, check_args(h && llr && ext && msg_llr, kNoList, B, [&] { return llr_fmt_check(fmt, llr); }), B, [&]() -> int {
+        int rc;
+        if ((rc = sys_prepare(h))) return rc;
+        SysTables &t = *h->sys;
+        if ((rc = stage_rows(h, llr, fmt, B))) return rc;
+        if ((rc = t.d_soft.ensure((size_t)B * (h->N + h->K)))) return rc;
+        HIP_TRY(hipMemcpy(t.d_soft.p, ext, (size_t)B * h->N * sizeof(double), hipMemcpyHostToDevice));
+        double *d_out = t.d_soft.p + (size_t)B * h->N;
+        HIP_TRY(polar_launch_sys_soft(h->d_in.p, fmt, t.d_soft.p, t.d_idx.p + 2 * (size_t)h->N + h->K, B, h->N, h->K, d_out, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return copy_back(msg_llr, 0, d_out, (size_t)B * h->K);
+    });
 }
 
 int polar_synth_sys_llr_dev(polar_code_t *h, int constellation, uint64_t seed, uint64_t trial0, long B, double s_or_snr, double *d_llr,
                             uint8_t *d_msg, uint8_t *d_u_info, void *stream) {
     int cid = 0;
-    int rc = check_args(h && d_llr, kNoList, B, [&] { return sys_constellation(constellation, &cid); });
-    if (rc || B == 0) return rc;
-    DevGuard dg_;
-    if ((rc = ensure_device(h, dg_))) return rc;
-    if ((rc = sys_prepare(h))) return rc;
-    SysTables &t = *h->sys;
-    if ((rc = t.d_coded.ensure((size_t)B * h->N))) return rc;
-    if (!d_msg) { if ((rc = t.d_msg.ensure((size_t)B * h->K))) return rc; d_msg = t.d_msg.p; }
-    return synth_launch(h, cid, seed, trial0, 1, B, s_or_snr, cid == 0, d_llr, d_msg, d_u_info, (hipStream_t)stream);
+    return on_device(h, check_args(h && d_llr, kNoList, B, [&] { return sys_constellation(constellation, &cid); }), B, [&]() -> int {
+        int rc;
+        if ((rc = sys_prepare(h))) return rc;
+        SysTables &t = *h->sys;
+        if ((rc = t.d_coded.ensure((size_t)B * h->N))) return rc;
+        if (!d_msg) { if ((rc = t.d_msg.ensure((size_t)B * h->K))) return rc; d_msg = t.d_msg.p; }
+        return synth_launch(h, cid, seed, trial0, 1, B, s_or_snr, cid == 0, d_llr, d_msg, d_u_info, (hipStream_t)stream);
+    });
 }
 
 // Per enabled (list size, point) and per chunk of trials, stream-ordered: the shared walk draws the trials' info bits (they are the
@@ -332,37 +322,19 @@ int polar_mc_batch_sys(polar_code_t *h, int constellation, uint64_t seed, uint64
                        const uint8_t *L, int n_L, const uint8_t *enabled, uint64_t *stats) {
     Sweep sw;
     int rc = sweep_begin(sw, h, axis && L && enabled && stats, "systematic sweep has", constellation, seed, t0, T, stride, axis,
-                         n_e > 0 && n_L > 0, stats, [&]() -> int {
-        for (int i = 0; i < n_L; ++i)
-            if (L[i] < 1 || L[i] > POLAR_MAX_LIST) return fail(POLAR_E_ARG, "list size %d out of range", (int)L[i]);
-        return POLAR_OK;
-    });
+                         n_e > 0 && n_L > 0, stats, [&] { return check_list_sizes(L, n_L); });
     if (rc || T == 0) return rc;
     const int N = h->N, K = h->K;
-    // a chunk: 512 MiB of LLR rows and their bytes, or the knob of the list calls
-    const long chunk = chunk_len(h, T, (size_t)512 << 20, (size_t)N * sizeof(double) + (size_t)N + 5 * (size_t)K);
+    const long chunk = sweep_chunk(h, T, (size_t)N * sizeof(double) + (size_t)N + 5 * (size_t)K);
     if ((rc = sys_prepare(h))) return rc;
     SysTables &t = *h->sys;
-    if ((rc = h->d_in.ensure((size_t)chunk * N)) || (rc = h->d_bytes_a.ensure((size_t)chunk * K)) || (rc = h->d_out.ensure((size_t)chunk * K)) ||
+    if ((rc = sweep_rows(h, chunk)) || (rc = h->d_out.ensure((size_t)chunk * K)) ||
         (rc = t.d_u.ensure((size_t)chunk * K)) || (rc = t.d_coded.ensure((size_t)chunk * N)) || (rc = t.d_mhat.ensure((size_t)chunk * K))) return rc;
-    std::vector<SweepCell> cells;
-    for (int li = 0; li < n_L; ++li)
-        for (int ie = 0; ie < n_e; ++ie)
-            if (enabled[li * n_e + ie]) cells.push_back({ie, chunk, (size_t)POLAR_SY_N * (li * n_e + ie), POLAR_SY_N});
-    const SweepCell *cur = nullptr;
-    long c0 = 0;                                       // trials of the current cell before this chunk
-    return sweep_walk(sw, cells, (size_t)POLAR_SY_N * n_e * n_L, [&](const SweepCell &cell, long c) -> int {
-        if (&cell != cur) { cur = &cell; c0 = 0; }
-        const int Ls = L[cell.ctr / POLAR_SY_N / n_e];
-        PolarEncodeParams p;
-        fill_enc(h, p);
-        p.B = c; p.seed = sw.seed; p.trial0 = sw.t0 + (uint64_t)c0 * (uint64_t)sw.stride; p.stride = sw.stride;
-        fill_channel(h, p, sw.cid, sw.axis[cell.point]);
-        p.llr = h->d_in.p;
-        c0 += c;
+    const auto cells = sweep_cells(enabled, n_L, n_e, POLAR_SY_N, std::vector<long>(n_L, chunk));
+    return sweep_walk(sw, cells, POLAR_SY_N, n_L, n_e, [&](const SweepCell &cell, long c, const PolarEncodeParams &p) -> int {
         if (int r = precode_launch(h, h->d_bytes_a.p, c, t.d_coded.p, t.d_u.p, nullptr)) return r;
         HIP_TRY(polar_launch_sys_channel(p, t.d_coded.p, nullptr));
-        if (int r = decode_impl(h, h->d_in.p, POLAR_LLR_F64, c, nullptr, Ls, h->d_out.p, nullptr, nullptr, nullptr, nullptr)) return r;
+        if (int r = decode_impl(h, h->d_in.p, POLAR_LLR_F64, c, nullptr, L[cell.row], h->d_out.p, nullptr, nullptr, nullptr, nullptr)) return r;
         if (int r = message_launch(h, h->d_out.p, c, t.d_mhat.p, nullptr)) return r;
         HIP_TRY(polar_launch_sys_classify(h->d_out.p, t.d_u.p, t.d_mhat.p, h->d_bytes_a.p, c, K, h->d_mc_ctr.p + cell.ctr, nullptr));
         return POLAR_OK;

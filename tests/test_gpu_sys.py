@@ -305,6 +305,33 @@ def test_sweep_counters_equal_the_composition(built_lib):
             assert (stats[li, ie] - 7).tolist() == want
 
 
+def test_sweep_counters_do_not_depend_on_the_chunks(built_lib):
+    """The same trials in one chunk and in chunks of 7 (45 trials: six whole chunks and one of 3; three enabled cells: the trial
+    offset of a chunk restarts twice), and split into the even and the odd ones: counts of the same trials, equal as integers."""
+    import polar_amd
+    g = _gpu((7, 64, 8))
+    Ls, axis, stride, t0, seed = (1, 4), (1.0, 2.5), 3, 40, 11
+    enabled = np.array([[1, 1], [0, 1]], np.uint8)
+
+    def run(T, t0, stride):
+        stats = np.full((len(Ls), len(axis), polar_amd.SY_N), 7, np.uint64)
+        g.mc_batch_sys(seed, t0, T, stride, axis, Ls, enabled, stats)
+        assert (stats[1, 0] == 7).all()                                # the disabled cell is untouched
+        return stats
+    whole = run(45, t0, stride)
+    g.debug_set("list_chunk_cw", 7)
+    try:
+        chunked = run(45, t0, stride)
+    finally:
+        g.debug_set("list_chunk_cw", 0)
+    print("one chunk", whole.tolist(), "chunks of 7", chunked.tolist())
+    assert (whole[enabled == 1, polar_amd.SY_RUN] == 7 + 45).all()
+    assert whole.tolist() == chunked.tolist()
+    # even and odd trials
+    halves = (run(22, t0, 2 * stride) - 7) + (run(22, t0 + stride, 2 * stride) - 7)
+    assert halves.tolist() == (run(44, t0, stride) - 7).tolist()
+
+
 # ---- 7. the point of it all ------------------------------------------------------------------------------------------------------------
 def test_message_ber_is_below_u_domain_ber(built_lib):
     """N = 128, K = 64, no CRC, L = 1, 2.5 dB, 4000 trials: a numpy min-sum SC model gives BIT_MSG / BIT_U = 0.43 on such trials."""
