@@ -400,6 +400,84 @@ int polar_mc_batch_sys(polar_code_t *h, int constellation, uint64_t seed, uint64
                        int n_e, const uint8_t *L, int n_L, const uint8_t *enabled /*[n_L*n_e]*/,
                        uint64_t *stats /*[n_L*n_e][POLAR_SY_N], ADDED to*/);
 
+/* ---- rate matching: puncturing, shortening, repetition ----
+ * (no member of the reference's class.) E coded bits are sent instead of the N = 2^n of the mother code. Conventions: z = butterfly(u)
+ * in natural order, coded[i] = z[bitrev(i)], an LLR > 0 means bit 0.
+ *   pattern  sel uint16 [E], 1 <= E <= 8 N: transmit position e carries coded[sel[e]]; known uint8 [N]: coded positions that are not
+ *            sent and are 0 in every codeword (shortened). A coded position in neither is punctured; a position that occurs several
+ *            times in sel is repeated.
+ *   schemes  polar_rm_pattern(n, E, scheme, Kp, sel, known) (host only, no handle; known is zero-filled first and may be NULL for
+ *            the schemes that set none; Kp = K + crc is read by POLAR_RM_NR alone):
+ *              POLAR_RM_PUNCTURE (E < N)  sel[e] = N - E + e;
+ *              POLAR_RM_SHORTEN  (E < N)  sel[e] = e, known[E .. N) = 1;
+ *              POLAR_RM_REPEAT   (E >= N) sel[e] = e mod N;
+ *              POLAR_RM_NR       (n >= 5) the sub-block interleaver and bit selection of 3GPP TS 38.212 §5.4.1 applied to z (NR's d):
+ *                                P32 = 0 1 2 4 3 5 6 7 8 16 9 17 10 18 11 19 12 20 13 21 14 22 15 23 24 25 26 28 27 29 30 31,
+ *                                J(j) = P32[floor(32 j / N)] (N / 32) + j mod (N / 32), y[j] = bitrev(J(j)) as a coded-row index;
+ *                                E >= N: sel[e] = y[e mod N]; else Kp / E <= 7 / 16: sel[e] = y[e + N - E] (puncture); else
+ *                                sel[e] = y[e], known[y[E .. N)] = 1 (shorten). The pattern only: NR's extra pre-freezing and its
+ *                                reliability sequence are not part of it.
+ *   forced   polar_rm_forced(n, sel, E, known, forced) (host only): the leaves a design for this pattern must freeze, as a mask
+ *            forced uint8 [N] by leaf index; their number is returned (negative: an error code): for every known coded position p every leaf b with
+ *            b & bitrev(p) == bitrev(p) (z is 0 there for every word exactly when all of them are frozen), and the zero-capacity
+ *            leaves of the punctured set: a boolean row in coded order, true at the punctured positions, through n stages of
+ *            [c1 | c2, c1 & c2] (c1 / c2 = the even / odd entries, the layout of calculate_awgn_polarization.m), then bit reversal.
+ *   recover  rx [B][E] of any POLAR_LLR_* format -> llr fp64 [B][N]: at a known position short_llr (a handle setting, finite, > 0,
+ *            1000.0 by convention); at every other position acc = +0.0, then acc = acc + widen(rx[b][e]) over the e with sel[e] = p in
+ *            ascending e — plain fp64 additions, no contraction, no reordering; a punctured position is +0.0. Bit patterns are the
+ *            contract.
+ * polar_set_rate_match(h, sel, E, known or NULL, short_llr): the pattern of the handle; E = 0 clears it. POLAR_E_ARG, with a message
+ * naming the first offender: E outside [1, 8 N], sel[e] >= N, a known position that is also sent, a leaf b >= bitrev(p) bitwise of a
+ * known position p that is unfrozen in this handle (the word would not be 0 there), short_llr not finite or not positive. A punctured
+ * pattern whose zero-capacity leaves are unfrozen is accepted: the caller's loss, not an inconsistency.
+ * polar_get_rate_match: E (0: none set), and where E > 0 sel [E], known [N], short_llr (any output may be NULL).
+ * polar_rate_match_batch[_dev]: coded uint8 [B][N] -> tx uint8 [B][E]. polar_rate_recover_batch[_dev]: rx [B][E] of fmt -> llr [B][N].
+ * polar_decode_scl_llr_rm_batch[_dev]: recover into the handle's scratch, then decode_scl_llr at list size L (out [B][K], d_pm [B] or
+ * NULL). A pattern with any punctured or known position decodes in the LLR-domain kernel family for that call (as polar_set_mode(h, 1)
+ * would, for this call only): the fast kernels would hand every such row to their fallback pass. A pure repetition pattern takes
+ * the handle's own choice.
+ * polar_snr_sqrt_linear_rm: polar_snr_sqrt_linear with E in place of N (NaN without a pattern).
+ * polar_synth_rm_llr_dev: the rate-matched workload: trial t = trial0 + b draws the info bits polar_synth_llr_dev draws for trial t,
+ * encodes them, and rx[b][e] = polar_synth_llr(s, coded[sel[e]], z_e), z_e = element e & 1 of polar_synth_noise_pair(seed, t, e >> 1)
+ * (include/polar_synth.h); d_rx fp64 [B][E], d_info [B][K] or NULL.
+ * polar_mc_batch_rm: like polar_mc_batch_list on the Eb/N0 axis (BPSK): every ENABLED (L, point) simulates the trials
+ * {t0 + i*stride : i < T} of that workload at s = polar_snr_sqrt_linear_rm(h, ebno), decodes them as polar_decode_scl_llr_rm_batch_dev
+ * does and ADDS to stats[(li*n_e + ie)*POLAR_RM_N + c].
+ * The _dev forms are stream-ordered with no host synchronisation, and two calls on one handle and one stream need nothing between
+ * them; the first call after polar_set_rate_match uploads the tables. Host forms: copies in, the launches, a wait, the copies out.
+ * POLAR_E_ARG before the device is touched: no pattern set, NULL handle or required pointer, unknown fmt, 16-bit rows at an odd
+ * address, a list size out of range, negative B / T, stride < 1; B = 0 (T = 0) is POLAR_OK and writes nothing.
+ * polar_ga_construction_init: the Gaussian-approximation design started from a per-position vector: init [n_points][N] in coded
+ * order takes the place of the mean LLR of polar_ga_construction (one block of N), then the same polarization, bit reversal, stable
+ * descending sort and prefix sums; the leaves with forced[leaf] != 0 (uint8 [N]; NULL: none) are moved to the END of every `order` row
+ * in ascending index, whatever their value (the phi tables are not exact at 0). bler_prefix follows the order that is returned. */
+#define POLAR_RM_PUNCTURE 0
+#define POLAR_RM_SHORTEN 1
+#define POLAR_RM_REPEAT 2
+#define POLAR_RM_NR 3
+int polar_rm_pattern(int n, int E, int scheme, int Kp, uint16_t *sel /*[E]*/, uint8_t *known /*[N]*/);
+int polar_rm_forced(int n, const uint16_t *sel, int E, const uint8_t *known /*[N] or NULL*/, uint8_t *forced /*[N], by leaf index*/);
+int polar_set_rate_match(polar_code_t *h, const uint16_t *sel, int E, const uint8_t *known /*[N] or NULL*/, double short_llr);
+int polar_get_rate_match(const polar_code_t *h, int *E, uint16_t *sel, uint8_t *known, double *short_llr);
+int polar_rate_match_batch(polar_code_t *h, const uint8_t *coded /*[B][N]*/, long B, uint8_t *tx /*[B][E]*/);
+int polar_rate_match_batch_dev(polar_code_t *h, const uint8_t *d_coded, long B, uint8_t *d_tx, void *stream);
+int polar_rate_recover_batch(polar_code_t *h, const void *rx /*[B][E] of fmt*/, int fmt, long B, double *llr /*[B][N]*/);
+int polar_rate_recover_batch_dev(polar_code_t *h, const void *d_rx, int fmt, long B, double *d_llr, void *stream);
+int polar_decode_scl_llr_rm_batch(polar_code_t *h, const void *rx, int fmt, long B, int L, uint8_t *out /*[B][K]*/);
+int polar_decode_scl_llr_rm_batch_dev(polar_code_t *h, const void *d_rx, int fmt, long B, int L, uint8_t *d_out, double *d_pm,
+                                      void *stream);
+double polar_snr_sqrt_linear_rm(const polar_code_t *h, double ebno_db);
+int polar_synth_rm_llr_dev(polar_code_t *h, uint64_t seed, uint64_t trial0, long B, double s, double *d_rx, uint8_t *d_info,
+                           void *stream);
+#define POLAR_RM_RUN 0      /* every trial */
+#define POLAR_RM_ERR 1      /* decoded info bits differ from the sent ones */
+#define POLAR_RM_BIT 2      /* wrong info bits */
+#define POLAR_RM_N 3
+int polar_mc_batch_rm(polar_code_t *h, uint64_t seed, uint64_t t0, long T, long stride, const double *ebno, int n_e, const uint8_t *L,
+                      int n_L, const uint8_t *enabled /*[n_L*n_e]*/, uint64_t *stats /*[n_L*n_e][POLAR_RM_N], ADDED to*/);
+int polar_ga_construction_init(int n, const double *init /*[n_points][N], coded order*/, const uint8_t *forced /*[N] by leaf index, or NULL*/,
+                               int n_points, double phi_dx, double *channels, uint16_t *order, double *bler_prefix);
+
 /* ---- PolarCode::decode_scl_p1(PolarCode.cpp:110-128; PolarCode.m:299-310) ---- */
 int polar_decode_scl_p1(polar_code_t *h, const double *p1 /*[N]*/, const double *p0 /*[N]*/, int L, uint8_t *out /*[K]*/);
 int polar_decode_scl_p1_batch(polar_code_t *h, const double *p1, const double *p0, long B, int L, uint8_t *out);

@@ -44,6 +44,9 @@ FLIP_MAX = 64
 SN_RUN, SN_ERR, SN_UNDET, SN_ITERS, SN_N = 0, 1, 2, 3, 4     # include/polar_amd.h POLAR_SN_*: columns of the SCAN statistics
 SCAN_MINSUM, SCAN_EARLY_STOP, SCAN_MAX_ITERS = 1, 2, 32      # include/polar_amd.h POLAR_SCAN_*
 SY_RUN, SY_ERR, SY_BIT_MSG, SY_BIT_U, SY_N = 0, 1, 2, 3, 4   # include/polar_amd.h POLAR_SY_*: columns of the systematic statistics
+RM_PUNCTURE, RM_SHORTEN, RM_REPEAT, RM_NR = 0, 1, 2, 3       # include/polar_amd.h POLAR_RM_*: the built-in rate-matching schemes
+RM_SCHEMES = {"puncture": RM_PUNCTURE, "shorten": RM_SHORTEN, "repeat": RM_REPEAT, "nr": RM_NR}
+RM_RUN, RM_ERR, RM_BIT, RM_N = 0, 1, 2, 3                    # ... and the columns of the rate-matched statistics
 
 
 def _llr_fmt_code(fmt):
@@ -120,6 +123,9 @@ def lib():
         L.polar_last_error.restype = C.c_char_p
         L.polar_snr_sqrt_linear.restype = C.c_double
         L.polar_snr_sqrt_linear.argtypes = [C.c_void_p, C.c_double]
+        if hasattr(L, "polar_snr_sqrt_linear_rm"):       # (POLAR_AMD_LIB may name an older build: A/B runs of the benchmark)
+            L.polar_snr_sqrt_linear_rm.restype = C.c_double
+            L.polar_snr_sqrt_linear_rm.argtypes = [C.c_void_p, C.c_double]
         _lib = L
     return _lib
 
@@ -585,6 +591,150 @@ class PolarCode:
         run = np.maximum(stats[:, :, SY_RUN], 1).astype(np.float64)
         return {"stats": stats, "bler": stats[:, :, SY_ERR] / run, "ber_msg": stats[:, :, SY_BIT_MSG] / (run * self.K),
                 "ber_u": stats[:, :, SY_BIT_U] / (run * self.K)}
+
+    # ---- rate matching ----------------------------------------------------
+    @classmethod
+    def from_gauss_approx_rm(cls, block_length, info_length, E, scheme, design_ebno_db, crc_size=0, crc_matrix=None, phi_dx=1e-5,
+                             seed=1):
+        """Code of E transmitted bits on the mother code of `block_length`, designed by the Gaussian approximation for the pattern
+        of `scheme` (rate_match_pattern): the start vector is 4 (K / E) 10^(Eb/N0 / 10) times the number of transmit positions
+        per coded position — 0 at a punctured one —, 1e4 at a known one; the forced leaves (rate_match_forced) go to the end of the
+        order; the first K + crc of it are unfrozen; the pattern is set on the handle. Sets ``bler_estimate`` and ``channels`` as
+        from_gauss_approx does."""
+        n = int(round(np.log2(block_length)))
+        if (1 << n) != block_length:
+            raise PolarError("block_length must be a power of two")
+        k = info_length + crc_size
+        if not 0 < k <= block_length:
+            raise PolarError("info_length + crc_size must lie in [1, block_length]")
+        sel, known = rate_match_pattern(n, E, scheme, k)
+        forced = rate_match_forced(n, sel, known)
+        if k > block_length - int(forced.sum()):
+            raise PolarError("info_length + crc_size exceeds the %d leaves this pattern leaves free" % (block_length - int(forced.sum())))
+        init = (4 * (info_length / E) * 10 ** (design_ebno_db / 10)) * np.bincount(sel, minlength=block_length).astype(np.float64)
+        init[known != 0] = 1e4
+        ch, order, pre = ga_construction_init(n, init[None, :], forced, phi_dx)
+        frozen = np.ones(block_length, np.uint8)
+        frozen[order[0, :k]] = 0
+        if crc_size and crc_matrix is None:      # PolarCode.m:83: crc_matrix = floor(2*rand(crc_size, info_length))
+            crc_matrix = np.random.default_rng(seed).integers(0, 2, (crc_size, info_length)).astype(np.uint8)
+        code = cls.from_tables(n, info_length, crc_size, frozen, order[0], crc_matrix)
+        code.set_rate_match(sel, known)
+        code.channels = ch[0]
+        code.bler_estimate = float(pre[0, k - 1])
+        return code
+
+    def set_rate_match(self, sel, known=None, short_llr=1000.0):
+        """The handle's rate-matching pattern (polar_set_rate_match): sel uint16 [E], known uint8 [N] or None."""
+        sel = np.ascontiguousarray(sel, np.uint16).reshape(-1)
+        if sel.size == 0:
+            raise PolarError("set_rate_match: sel is empty (clear_rate_match removes a pattern)")
+        kn = None
+        if known is not None:
+            kn = np.ascontiguousarray(known, np.uint8)
+            if kn.shape != (self.N,):
+                raise PolarError("set_rate_match: known must have N entries")
+        self._chk(self._L.polar_set_rate_match(self._h, _p(sel, _u16p), C.c_int(sel.size), _p(kn, _u8p) if kn is not None else None,
+                                               C.c_double(short_llr)))
+
+    def clear_rate_match(self):
+        self._chk(self._L.polar_set_rate_match(self._h, None, C.c_int(0), None, C.c_double(0.0)))
+
+    def rate_match_info(self):
+        """(sel uint16 [E], known uint8 [N], short_llr) of the pattern set (polar_get_rate_match), or None."""
+        E, s = C.c_int(), C.c_double()
+        self._chk(self._L.polar_get_rate_match(self._h, C.byref(E), None, None, None))
+        if E.value == 0:
+            return None
+        sel, known = np.zeros(E.value, np.uint16), np.zeros(self.N, np.uint8)
+        self._chk(self._L.polar_get_rate_match(self._h, C.byref(E), _p(sel, _u16p), _p(known, _u8p), C.byref(s)))
+        return sel, known, s.value
+
+    def _rm_E(self):
+        E = C.c_int()
+        self._chk(self._L.polar_get_rate_match(self._h, C.byref(E), None, None, None))
+        if E.value == 0:
+            raise PolarError("no rate-matching pattern set (set_rate_match)")
+        return E.value
+
+    def rate_match(self, coded):
+        """coded [..., N] -> tx [..., E] = coded[..., sel] (polar_rate_match_batch)."""
+        E = self._rm_E()
+        c = np.ascontiguousarray(coded, np.uint8)
+        if c.ndim < 1 or c.shape[-1] != self.N:
+            raise PolarError(f"rate_match: coded must be [..., {self.N}], got shape {c.shape}")
+        c2 = c.reshape(-1, self.N)
+        tx = np.zeros((c2.shape[0], E), np.uint8)
+        self._chk(self._L.polar_rate_match_batch(self._h, _p(c2, _u8p), C.c_long(c2.shape[0]), _p(tx, _u8p)))
+        return tx.reshape(c.shape[:-1] + (E,))
+
+    def rate_recover(self, rx, fmt=None):
+        """rx [B, E] (or [E]; `fmt` as decode_scl_llr) -> the mother code's LLR rows float64 [B, N] (polar_rate_recover_batch):
+        short_llr at a known position, the sum of the received values of a position in transmit order, +0.0 at a punctured one."""
+        E = self._rm_E()
+        code, a = _llr_rows(rx, fmt)
+        if a.ndim < 1 or a.shape[-1] != E:
+            raise PolarError(f"rate_recover: rx must be [..., {E}], got shape {a.shape}")
+        a2 = a.reshape(-1, E)
+        out = np.zeros((a2.shape[0], self.N), np.float64)
+        self._chk(self._L.polar_rate_recover_batch(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(a2.shape[0]), _p(out, _dp)))
+        return out[0] if a.ndim == 1 else out
+
+    def decode_scl_llr_rm(self, rx, list_size, out=None, fmt=None):
+        """decode_scl_llr of the rate-matched rows rx [B, E] (or [E]): rate_recover, then the decoder, in one call
+        (polar_decode_scl_llr_rm_batch). `out` and `fmt` as decode_scl_llr."""
+        E = self._rm_E()
+        code, a = _llr_rows(rx, fmt)
+        if a.ndim < 1 or a.shape[-1] != E:
+            raise PolarError(f"decode_scl_llr_rm: rx must be [..., {E}], got shape {a.shape}")
+        a2 = a.reshape(-1, E)
+        if out is None:
+            out = np.zeros((a2.shape[0], self.K), np.uint8)
+        elif out.dtype != np.uint8 or out.shape != (a2.shape[0], self.K) or not out.flags.c_contiguous:
+            raise PolarError("out must be a C-contiguous uint8 array of shape [B, K]")
+        self._chk(self._L.polar_decode_scl_llr_rm_batch(self._h, C.c_void_p(a2.ctypes.data), C.c_int(code), C.c_long(a2.shape[0]),
+                                                        C.c_int(list_size), _p(out, _u8p)))
+        return out[0] if a.ndim == 1 else out
+
+    def rate_match_dev(self, coded_ptr, B, tx_ptr, stream=None):
+        """Device-resident form (polar_rate_match_batch_dev): coded uint8 [B, N] -> tx uint8 [B, E]."""
+        self._chk(self._L.polar_rate_match_batch_dev(self._h, C.c_void_p(coded_ptr), C.c_long(B), C.c_void_p(tx_ptr), _stream_ptr(stream)))
+
+    def rate_recover_dev(self, rx_ptr, fmt, B, llr_ptr, stream=None):
+        """Device-resident form (polar_rate_recover_batch_dev): rx [B, E] of `fmt` -> llr float64 [B, N]."""
+        self._chk(self._L.polar_rate_recover_batch_dev(self._h, C.c_void_p(rx_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B),
+                                                       C.c_void_p(llr_ptr), _stream_ptr(stream)))
+
+    def decode_scl_llr_rm_dev(self, rx_ptr, fmt, B, list_size, out_ptr, pm_ptr=0, stream=None):
+        """Device-resident form (polar_decode_scl_llr_rm_batch_dev): rx [B, E] of `fmt` -> out uint8 [B, K], pm float64 [B]."""
+        self._chk(self._L.polar_decode_scl_llr_rm_batch_dev(self._h, C.c_void_p(rx_ptr), C.c_int(_llr_fmt_code(fmt)), C.c_long(B),
+                                                            C.c_int(list_size), C.c_void_p(out_ptr), C.c_void_p(pm_ptr), _stream_ptr(stream)))
+
+    def snr_sqrt_linear_rm(self, ebno_db):
+        return self._L.polar_snr_sqrt_linear_rm(self._h, C.c_double(ebno_db))
+
+    def synth_rm_llr_dev(self, seed, trial0, B, s, rx_ptr, info_ptr=0, stream=None):
+        """polar_synth_rm_llr_dev: the rate-matched workload's trials trial0 .. trial0 + B - 1: rx float64 [B, E], info uint8 [B, K]."""
+        self._chk(self._L.polar_synth_rm_llr_dev(self._h, C.c_uint64(seed), C.c_uint64(trial0), C.c_long(B), C.c_double(s),
+                                                 C.c_void_p(rx_ptr), C.c_void_p(info_ptr), _stream_ptr(stream)))
+
+    def mc_batch_rm(self, seed, t0, T, stride, ebno_vec, list_size_vec, enabled, stats):
+        """polar_mc_batch_rm: the trials {t0 + i*stride : i < T} of the rate-matched workload of every enabled (L, Eb/N0) ADD to
+        stats, uint64 [len(L), len(ebno), 3] = RM_RUN, RM_ERR, RM_BIT."""
+        Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        fn = lambda h, _cid, *rest: self._L.polar_mc_batch_rm(h, *rest)       # (the sweep has no constellation argument: BPSK)
+        self._mc_batch_cells(fn, seed, t0, T, stride, ebno_vec, Ls, enabled, stats, 0, RM_N, True)
+
+    def rm_stats(self, axis, list_size_vec, max_runs=1000, max_err=100, seed=0, batch=0):
+        """The rate-matched code over an Eb/N0 sweep: rounds of mc_batch_rm, sized and stopped like list_stats' (_stat_rounds).
+        Returns a dict: `stats` uint64 [len(L), len(axis), 3] (RM_* columns), `bler` = ERR / RUN, `ber` = BIT / (RUN K)."""
+        ax = np.ascontiguousarray(axis, np.float64)
+        Ls = np.ascontiguousarray(list_size_vec, np.uint8)
+        stats = np.zeros((len(Ls), len(ax), RM_N), np.uint64)
+        self._stat_rounds("rm_stats", lambda t0, T, enabled: self.mc_batch_rm(seed, t0, T, 1, ax, Ls, enabled, stats),
+                          stats, RM_ERR, RM_RUN, max_runs, max_err, batch)
+        run = np.maximum(stats[:, :, RM_RUN], 1).astype(np.float64)
+        return {"stats": stats, "bler": stats[:, :, RM_ERR] / run, "ber": stats[:, :, RM_BIT] / (run * self.K)}
 
     # ---- decoders -----------------------------------------------------------------------
     def decode_scl_llr(self, llr, list_size, out=None, fmt=None, systematic=False):
@@ -1156,6 +1306,55 @@ class PolarCode:
             raise failure[0]
         _check(rc)
         return out, ber, {"err": err, "run": run, "rounds": int(rounds.value), "steps": self.debug_get("round_us_count")}
+
+
+def _rm_scheme(scheme):
+    if isinstance(scheme, str):
+        if scheme not in RM_SCHEMES:
+            raise PolarError(f"unknown rate-matching scheme {scheme!r} (supported: {sorted(RM_SCHEMES)})")
+        return RM_SCHEMES[scheme]
+    return int(scheme)
+
+
+def rate_match_pattern(n, E, scheme, Kp=None):
+    """(sel uint16 [E], known uint8 [N]) of a built-in scheme (polar_rm_pattern; host only): "puncture", "shorten", "repeat" or
+    "nr" (Kp = K + crc decides between NR's puncturing and shortening)."""
+    if E < 1:
+        raise PolarError("rate_match_pattern: E must be positive")
+    sel, known = np.zeros(int(E), np.uint16), np.zeros(1 << n if 0 < n < 31 else 1, np.uint8)
+    _check(lib().polar_rm_pattern(C.c_int(n), C.c_int(E), C.c_int(_rm_scheme(scheme)), C.c_int(0 if Kp is None else Kp),
+                                  _p(sel, _u16p), _p(known, _u8p)))
+    return sel, known
+
+
+def rate_match_forced(n, sel, known=None):
+    """The leaves a design for this pattern must freeze, as a mask uint8 [N] by leaf index (polar_rm_forced; host only)."""
+    sel = np.ascontiguousarray(sel, np.uint16).reshape(-1)
+    kn = None if known is None else np.ascontiguousarray(known, np.uint8)
+    forced = np.zeros(1 << n if 0 < n < 31 else 1, np.uint8)
+    if kn is not None and kn.shape != forced.shape:
+        raise PolarError("rate_match_forced: known must have N entries")
+    _check(lib().polar_rm_forced(C.c_int(n), _p(sel, _u16p), C.c_int(sel.size), _p(kn, _u8p) if kn is not None else None,
+                                 _p(forced, _u8p)))
+    return forced
+
+
+def ga_construction_init(num_layers, init, forced=None, phi_dx=1e-5):
+    """polar_ga_construction_init: the Gaussian-approximation design started from init [n_points, N] (coded order) ->
+    (channels [n_points, N], order uint16 [n_points, N], bler_prefix [n_points, N]); the leaves with forced[leaf] != 0 end every
+    order row, in ascending index."""
+    N = 1 << num_layers
+    a = np.ascontiguousarray(init, np.float64)
+    if a.ndim != 2 or a.shape[1] != N:
+        raise PolarError("ga_construction_init: init must be [n_points, N]")
+    f = None if forced is None else np.ascontiguousarray(forced, np.uint8)
+    if f is not None and f.shape != (N,):
+        raise PolarError("ga_construction_init: forced must have N entries")
+    P = a.shape[0]
+    ch, order, pre = np.zeros((P, N)), np.zeros((P, N), np.uint16), np.zeros((P, N))
+    _check(lib().polar_ga_construction_init(C.c_int(num_layers), _p(a, _dp), _p(f, _u8p) if f is not None else None, C.c_int(P),
+                                            C.c_double(phi_dx), _p(ch, _dp), _p(order, _u16p), _p(pre, _dp)))
+    return ch, order, pre
 
 
 def _sweep_id(constellation, receiver):

@@ -34,10 +34,11 @@ SOURCES = [("polar_kernels.hip", ["POLAR_ED_TU=0"], "", []), ("polar_kernels.hip
            ("polar_kernels_sc.hip", [], "", []), ("polar_kernels_p1.hip", [], "", []), ("polar_channel.hip", [], "", []),
            ("polar_construct.hip", [], "", []), ("polar_kernels_mlc.hip", [], "", []), ("polar_kernels_ga.hip", [], "", []),
            ("polar_kernels_metric.hip", [], "", []), ("polar_kernels_adapt.hip", [], "", []),
-           ("polar_kernels_flip.hip", [], "", []), ("polar_kernels_scan.hip", [], "", []), ("polar_kernels_sys.hip", [], "", [])] + \
+           ("polar_kernels_flip.hip", [], "", []), ("polar_kernels_scan.hip", [], "", []), ("polar_kernels_sys.hip", [], "", []),
+           ("polar_kernels_rm.hip", [], "", [])] + \
           [(f, [], "", []) for f in ("polar_handle.cpp", "polar_decode.cpp", "polar_hostpipe.cpp", "polar_montecarlo.cpp", "polar_multi.cpp",
                                      "polar_debug.cpp", "polar_ga.cpp", "polar_bicm.cpp", "polar_list.cpp", "polar_mlc.cpp", "polar_adaptive.cpp", "polar_flip.cpp",
-                                     "polar_scan.cpp", "polar_sys.cpp")]
+                                     "polar_scan.cpp", "polar_sys.cpp", "polar_rm.cpp")]
 # the test build (libpolar_amd_test.so): the same objects, except that these are compiled again with -DPOLAR_TEST_HOOKS —
 # the fault-injection keys of include/polar_amd_debug.h exist only there
 TEST_HOOK_SOURCES = ("polar_montecarlo.cpp", "polar_debug.cpp")

@@ -324,6 +324,28 @@ public:
         check(polar_get_sys_positions(_h, pos.data(), nullptr));
         return pos;
     }
+    // Rate matching (polar_set_rate_match, polar_rate_match_batch, polar_decode_scl_llr_rm_batch): transmit position e
+    // carries coded[sel[e]]; `known` (empty: none) marks the coded positions that are not sent and are 0 in every codeword. rate_match:
+    // B codewords back to back -> B rows of sel.size() bits; decode_scl_llr_rm: B received rows of sel.size() LLRs -> the decoded info.
+    void set_rate_match(const std::vector<uint16_t> &sel, const std::vector<uint8_t> &known = {}, double short_llr = 1000.0) {
+        need(known.empty() || known.size() == _block_length, "set_rate_match: known must be empty or hold block_length entries");
+        check(polar_set_rate_match(_h, sel.data(), (int)sel.size(), known.empty() ? nullptr : known.data(), short_llr));
+        _rm_length = sel.size();
+    }
+    std::vector<uint8_t> rate_match(const std::vector<uint8_t> &coded) {
+        need(_rm_length && coded.size() % _block_length == 0, "rate_match: no pattern set, or size not a multiple of block_length");
+        const long B = (long)(coded.size() / _block_length);
+        std::vector<uint8_t> tx((size_t)B * _rm_length);
+        if (B) check(polar_rate_match_batch(_h, coded.data(), B, tx.data()));
+        return tx;
+    }
+    std::vector<uint8_t> decode_scl_llr_rm(const std::vector<double> &rx, uint16_t list_size) {
+        need(_rm_length && rx.size() % _rm_length == 0, "decode_scl_llr_rm: no pattern set, or size not a multiple of the transmit length");
+        const long B = (long)(rx.size() / _rm_length);
+        std::vector<uint8_t> out((size_t)B * _info_length);
+        if (B) check(polar_decode_scl_llr_rm_batch(_h, rx.data(), POLAR_LLR_F64, B, list_size, out.data()));
+        return out;
+    }
     // Symbol-domain BICM receiver (PolarM/Constellation.m:123-144 in front of decode_scl_llr): received symbols, block_length /
     // n_bits per codeword, with noise variance n0 -> the bits decode_scl_llr gives on compute_llr_bicm's LLRs of them.
     // constellation_name as the reference's Constellation constructor takes it ("bpsk", "ask4-gray", ... "ask16-sp").
@@ -437,6 +459,7 @@ private:
     polar_code_t *_h = nullptr;
     uint8_t _n;
     uint16_t _info_length, _block_length = 0, _crc_size;
+    size_t _rm_length = 0;           // transmit positions of the rate-matching pattern set (0: none)
     std::vector<double> _channels;
 };
 

@@ -395,6 +395,7 @@ void polar_destroy(polar_code_t *h) {
     if (h->pin_in) (void)hipHostFree(h->pin_in);
     if (h->pin_out) (void)hipHostFree(h->pin_out);
     sys_release(h);
+    rm_release(h);
     h->d_flip_ops.release(); h->d_flip_i32.release(); h->d_scan_ops.release(); h->d_sc_ops.release(); h->d_sc_lat_ops.release(); h->d_flag_words.release(); h->d_var_scr.release(); h->d_tab_scr.release(); h->d_head_rec.release();
     delete h;
 }

@@ -12,6 +12,8 @@
 //   polar_flip.cpp        SC-Flip: CRC-aided single-bit retries of SC decoding, and its sweep
 //   polar_scan.cpp        SCAN: soft-output decoding by soft cancellation, and its sweep
 //   polar_sys.cpp         systematic coding: its host tables, precode / message recovery / soft message outputs, its workload and sweep
+//   polar_rm.cpp          rate matching: patterns, forced leaves, the handle's pattern and its inverse tables, select / recover, the
+//                         rate-matched decode, workload and sweep, the GA construction from a start vector
 //   polar_bicm.cpp        Constellation mirror: modulate, BICM demapper, decode from received symbols
 //   polar_montecarlo.cpp  get_bler_quick: device-side rounds, the driver of the pipelined rounds, Monte-Carlo code construction;
 //                         the walk the sweeps of the five decoder variants share (sweep_begin, sweep_cells, sweep_walk)
@@ -227,6 +229,7 @@ struct HostPipe {
 };
 
 struct SysTables;
+struct RmTables;
 
 struct polar_code {
     int n = 0, N = 0, K = 0, crc = 0;
@@ -290,6 +293,7 @@ struct polar_code {
     std::vector<uint32_t> scan_ops;  // SCAN: the walk of scan_kernel (PolarScanParams::ops), built and uploaded by the first call (polar_scan.cpp)
     DevBuf<uint32_t> d_scan_ops;
     SysTables *sys = nullptr;        // systematic coding: host tables, their device copies and staging, built by the first systematic call and dropped by polar_set_crc_matrix (polar_sys.cpp)
+    RmTables *rm = nullptr;          // rate matching: the pattern set by polar_set_rate_match, its inverse tables, their device copies and scratch (polar_rm.cpp)
     DevBuf<double> d_bicm_llr;       // symbol-domain BICM receiver: the demapped LLR rows [B][N] that decode_impl reads (polar_bicm.cpp)
     int mode = 0;                    // 0 auto, 1 LLR-domain kernel only, 2 exp-domain kernel + fallback pass
     // Measurement / test knobs. The environment is read ONCE, when the handle is created (read_env_knobs): a decode never
@@ -537,6 +541,8 @@ using SweepBody = std::function<int(const SweepCell &, long, const PolarEncodePa
 int sweep_walk(Sweep &sw, const std::vector<SweepCell> &cells, int width, int n_rows, int n_e, const SweepBody &body);
 // polar_sys.cpp — drops the systematic tables and their device buffers (polar_destroy, polar_set_crc_matrix)
 void sys_release(polar_code *h);
+// polar_rm.cpp — drops the rate-matching pattern and its device buffers (polar_destroy, polar_set_rate_match)
+void rm_release(polar_code *h);
 // polar_hostpipe.cpp
 // rows that are received symbols instead of LLRs (polar_decode_bicm_batch*): M elements per row, demapped on the device
 struct SymRows { int cid, M; double n0; };
